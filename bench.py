@@ -103,6 +103,15 @@ def summarize(recs, peak_tflops):
             "top": sorted(mm, key=lambda r: -r[4])[:6]}
 
 
+def writable_dir(path):
+    """``path``, created if missing, when this process can write into it; None when it cannot (a read-only checkout)"""
+    try:
+        os.makedirs(path, exist_ok=True)
+    except OSError:
+        return None
+    return path if os.access(path, os.W_OK) else None
+
+
 def dump_launches(path, recs):
     with open(path, "w") as f:
         for k, n, fl, by, ms, kn in recs:
@@ -176,7 +185,7 @@ def wl_tocg_infer(ctx, mixed, B):
     i1, i2 = tocg_inputs(torch, B, ctx["hdist"].shard_seed(1234, ctx["rank"]), ctx["dev"])
 
     def step(_i):
-        model(opt, i1, i2)
+        return model(opt, i1, i2)
 
     def parity():
         """configs[1] outputs vs the oracle at 1024x768 (1 image): max-rel errors and the argmax label map -- every
@@ -205,6 +214,7 @@ def wl_tocg_infer(ctx, mixed, B):
                 "mismatch_top2_margin_ulps_of_logit": [round(u, 1) for u in ulps[:16]],
                 "mismatch_top2_margin_max_abs": float(margin.max().item()) if margin.numel() else 0.0}
     return dict(step=step, B=B, train=False, parity=parity, flops_per_img=1.468e12,
+                outputs=lambda r: {"flow": r[0], "fake_segmap": r[1], "warped_cloth": r[2], "warped_clothmask": r[3]},
                 metric="1024x768 try-on images/sec (ConditionGenerator inference: flow+seg+grid_sample)",
                 workload="BASELINE configs[1]: ConditionGenerator inference 1024x768 fp32, ngf=96, random-init weights",
                 traffic_tag="tocg_infer")
@@ -243,7 +253,7 @@ def wl_train_condition(ctx, mixed, B):
 
     def step(_i):
         _T.MMA_BF16[0] = bool(mixed)     # (another workload of this process may have switched it)
-        condition_train_step(opt, tocg, D, l1, crit_vgg, gan, og, od, batch, sg, sd)
+        return condition_train_step(opt, tocg, D, l1, crit_vgg, gan, og, od, batch, sg, sd)
 
     def parity():
         """fp32 (BASELINE configs[2]): ONE image at the timed resolution, 1x1024x768 ngf=96, against torch autograd over the
@@ -258,6 +268,7 @@ def wl_train_condition(ctx, mixed, B):
         finally:
             _T.MMA_BF16[0] = bool(mixed)
     return dict(step=step, B=B, train=True, parity=parity, flops_per_img=13.2e12,
+                outputs=lambda r: {"loss": r, "tocg_params": flat_params(torch, tocg), "D_params": flat_params(torch, D)},
                 metric="1024x768 images/sec (train_condition.py step: tocg fwd/bwd with batch-stat BN, 5 VGG pairs, LSGAN D, Adam)",
                 workload="BASELINE configs[2]: train_condition.py 1024x768 --Ddownx2 --lasttvonly --interflowloss, ngf=96, "
                          "random-init weights", traffic_tag="train_condition")
@@ -307,17 +318,17 @@ def wl_generator(ctx, mixed, B, train):
         def step(_i):
             _T.MMA_BF16[0] = bool(mixed)     # (another workload of this process may have switched it)
             x, parse7 = make_generator_inputs(opt, tocg, batch)
-            generator_train_step(opt, gen, dis, cg, cf, crit_vgg, og, od, x, parse7, batch["image"], sg, sd)
+            return generator_train_step(opt, gen, dis, cg, cf, crit_vgg, og, od, x, parse7, batch["image"], sg, sd)
 
         def parity():
             from oracle import step_check
             gp = os.path.join(ROOT, "gpurun_out")
-            os.makedirs(gp, exist_ok=True)
+            gp = writable_dir(gp)       # None in a read-only checkout: the per-parameter tables are skipped, the numbers are not
             engines = (False, True) if mixed else (False,)
             # at the bench resolution with two images: the size-gated kernels of the timed path (patch tiles, LDS-DMA weight
             # gradients, thin convolutions, sub-batch launches) are the ones compared (~30 s of CPU autograd)
             reps = step_check.compare_generator_step(1024, 768, 64, 64, 2, seed=1, mixed=engines, cpu_threads=ctx["cpu_threads"],
-                                                     table_path=os.path.join(gp, "bench_grad_parity_gen.txt"))
+                                                     table_path=gp and os.path.join(gp, "bench_grad_parity_gen.txt"))
             out = {"fp32_engine_vs_oracle": reps[False],
                    "tolerance_fp32": "image / losses 1e-3 rel (north star); per-parameter gradients 2e-2 of max(|g|, 1e-3 module max)",
                    "tolerance_short": "fp32 engine: image, losses 1e-3 rel, grads 2e-2 of max|g|"}
@@ -332,7 +343,7 @@ def wl_generator(ctx, mixed, B, train):
                                          "2e-3 rel, gradient cosine >= 0.99 on every sizeable parameter")
             # the discriminator half of the same iteration (train_generator.py:327-360): D losses, every D gradient, D's Adam step
             dreps = step_check.compare_discriminator_step(1024, 768, 64, 64, 2, seed=1, mixed=engines, cpu_threads=ctx["cpu_threads"],
-                                                          table_path=os.path.join(gp, "bench_grad_parity_dis.txt"))
+                                                          table_path=gp and os.path.join(gp, "bench_grad_parity_dis.txt"))
             out["discriminator_half_fp32_engine_vs_oracle"] = dreps[False]
             if mixed:
                 out["discriminator_half_bf16_engine_vs_oracle"] = dreps[True]
@@ -360,6 +371,8 @@ def wl_generator(ctx, mixed, B, train):
             from hr_viton_amd.graph import GraphedIteration
             timed = (lambda gi: (lambda _i: gi()))(GraphedIteration(lambda: step(0), (og, od), warmup=3))
         return dict(step=step, timed=timed, B=B, train=True, parity=parity, cpu_baseline=cpu_baseline, flops_per_img=8.8e12,
+                    outputs=lambda r: {"loss": r[0], "output_paired": r[1], "generator_params": flat_params(torch, gen),
+                                       "discriminator_params": flat_params(torch, dis)},
                     metric="1024x768 try-on images/sec (train_generator.py step: tocg+glue, G fwd/bwd, D fwd/bwd x2, VGG, Adam)",
                     workload="BASELINE configs[3] (SURVEY 8d config #4, headline): train_generator.py 1024x768, "
                              f"{B} img/GPU, " + ("--fp16 (bf16 MFMA operands, fp32 accumulate)" if mixed else "fp32") +
@@ -370,7 +383,7 @@ def wl_generator(ctx, mixed, B, train):
     gen.eval()
 
     def step(_i):
-        tryon_step(opt, tocg, gen, batch)
+        return tryon_step(opt, tocg, gen, batch)
     timed, gr = None, None
     if ctx["args"].graph or ctx.get("force_graph"):
         from hr_viton_amd.graph import graphed_tryon
@@ -411,10 +424,82 @@ def make_workload(ctx, name, mixed, B):
     return wl_generator(ctx, mixed, B, train=(name == "train_generator"))
 
 
-def measure(ctx, wl, steps, warmup, mixed, dump=None):
+def flat_params(torch, module):
+    """every parameter of ``module`` in registration order, as one flat fp32 vector"""
+    return torch.cat([p.detach().reshape(-1).float() for p in module.parameters()])
+
+
+def named_arrays(obj, prefix=""):
+    """what a step returned (tensors, Act views, dicts, lists, tuples) -> {name: tensor}; names join the keys / indices with '_'"""
+    out = {}
+    if isinstance(obj, dict):
+        items = obj.items()
+    elif isinstance(obj, (list, tuple)):
+        items = enumerate(obj)
+    else:
+        if hasattr(obj, "coff") and hasattr(obj, "C"):        # an ops.Act: its C real channels of the padded NHWC tensor
+            obj = obj.t[..., obj.coff:obj.coff + obj.C]
+        if hasattr(obj, "detach"):
+            out[prefix] = obj
+        return out
+    for k, v in items:
+        out.update(named_arrays(v, f"{prefix}_{k}" if prefix else str(k)))
+    return out
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """{name: tensor} -> ``path``/<name>.npy, float64 kept, everything else (bf16, label maps, masks) as float32.  At most ``limit``
+    bytes in all: when the arrays do not fit, each keeps min(its size, L) bytes with L the largest level that fits (small arrays stay
+    whole, the large ones share the rest), an array cut down being written flat as the elements at fixed seeded positions -- one in
+    each of k equal strata of its flat index -- so that two runs or two builds write the same positions.  Returns {name: shape written}."""
+    import zlib
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: (t.detach() if t.dtype == torch.float64 else t.detach().float()) for k, t in arrays.items()}
+    room = limit - 128 * len(arrays)           # (the .npy header of each file)
+    keep, order = {}, sorted(arrays, key=lambda k: arrays[k].numel() * arrays[k].element_size())
+    for i, k in enumerate(order):
+        t = arrays[k]
+        share = room // (len(order) - i)
+        keep[k] = min(t.numel(), share // t.element_size())
+        room -= keep[k] * t.element_size()
+    written = {}
+    for k in order:
+        t, n = arrays[k], arrays[k].numel()
+        if keep[k] < n:
+            g = torch.Generator().manual_seed(zlib.crc32(k.encode()))
+            pos = (torch.arange(keep[k], dtype=torch.float64) + torch.rand(keep[k], generator=g, dtype=torch.float64)) * (n / keep[k])
+            t = t.reshape(-1)[pos.long().clamp_(max=n - 1).to(t.device)]
+        a = t.cpu().numpy()
+        np.save(os.path.join(path, k + ".npy"), a)
+        written[k] = list(a.shape)
+    return written
+
+
+def timed_region(ctx, wl, steps, warmup, device_sync, dump_dir=None):
+    """``warmup`` + exactly ``steps`` timed calls of the workload's timed path; seconds of the timed ones.  ``dump_dir``: what the last
+    timed step returned (named by wl["outputs"]) is written there by rank 0 after the clock has stopped."""
+    step, last = wl.get("timed") or wl["step"], {}
+
+    def keep(i):
+        last["out"] = step(i)
+    dt = ctx["hdist"].timed_steps(keep if dump_dir else step, steps, warmup, device_sync)
+    if dump_dir and ctx["rank"] == 0:
+        arrays = named_arrays(wl.get("outputs", lambda r: r)(last.pop("out")))
+        written = dump_outputs(dump_dir, arrays)
+        _log(f"outputs of the last timed step -> {dump_dir}: " + ", ".join(
+            f"{k}{tuple(s)}" + ("" if s == list(arrays[k].shape) else f" sampled from {tuple(arrays[k].shape)}") for k, s in written.items()))
+    return dt
+
+
+def measure(ctx, wl, steps, warmup, mixed, dump=None, dump_dir=None):
     """Timed region (driver contract) + one extra profiled step with per-launch HIP events."""
-    torch, hdist, ops = ctx["torch"], ctx["hdist"], ctx["ops"]
-    dt = hdist.timed_steps(wl.get("timed") or wl["step"], steps, warmup, torch.cuda.synchronize)
+    torch, ops = ctx["torch"], ctx["ops"]
+    dt = timed_region(ctx, wl, steps, warmup, torch.cuda.synchronize, dump_dir)
     ops.profile_begin()
     wl["step"](0)
     recs = ops.profile_end(kernels=True)
@@ -668,6 +753,7 @@ def wl_stub(ctx, B):
         y = (w @ w).sum().reshape(1)
         if tdist.is_initialized():
             tdist.all_reduce(y)        # the data-path collective of the training workloads (gradient all-reduce)
+        return {"y": y}
     return dict(step=step, B=B, train=True, parity=None, flops_per_img=0.0, metric="stub (plumbing test, not a measurement)",
                 workload="stub: CPU matmul + all-reduce", traffic_tag="stub")
 
@@ -681,6 +767,10 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="skip the configs[4] / configs[1] sub-measurements")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads for the CPU legs (0 = min(cores, 32))")
     ap.add_argument("--dump-launches", default=None, help="write the per-launch table of one step to this file")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path returned in its last timed step (a training workload: also the updated weights) "
+                         "as DIR/<name>.npy, float32 or float64, at most 64 MB in all (larger arrays: a fixed seeded sample); the "
+                         "inputs are seeded, so two builds run with the same arguments can be compared array for array")
     ap.add_argument("--workload", default="train_generator",
                     choices=["train_generator", "tryon_infer", "tocg_infer", "train_condition", "stub"],
                     help="train_generator = BASELINE configs[3], the headline (default); tryon_infer = configs[4]; "
@@ -694,6 +784,8 @@ def main():
     ap.add_argument("--graph", action="store_true", help="tryon_infer / train_generator: replay the step as one captured hipGraph (train_generator on N > 1 GPUs: graph "
                          "segments with the gradient all-reduces between them)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     mixed = (args.workload in ("train_generator", "tryon_infer") or args.bf16) and not args.fp32
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))
@@ -713,7 +805,7 @@ def main():
     if args.workload == "stub":
         ctx = dict(torch=torch, nn=nn, hdist=hdist, ops=ops, rank=rank, world=world, dev=torch.device("cpu"), args=args)
         wl = wl_stub(ctx, args.batch)
-        dt = hdist.timed_steps(wl["step"], args.steps, args.warmup, None)
+        dt = timed_region(ctx, wl, args.steps, args.warmup, None, args.dump_outputs)
         if rank == 0:
             print(json.dumps({"metric": wl["metric"], "value": round(wl["B"] * world * args.steps / dt, 3), "unit": "images/s",
                               "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -737,7 +829,7 @@ def main():
     _log(f"building workload {args.workload} ({'bf16' if mixed else 'fp32'})")
     wl = make_workload(ctx, args.workload, mixed, args.batch)
     _log("timed region")
-    res = measure(ctx, wl, args.steps, args.warmup, mixed, args.dump_launches)
+    res = measure(ctx, wl, args.steps, args.warmup, mixed, args.dump_launches, args.dump_outputs)
     _log(f"{res['value']} images/s, {res['ms_per_step']} ms/step")
     res["steps"] = args.steps
     s = res["summary"]

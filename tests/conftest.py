@@ -7,6 +7,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 GOLDEN = os.path.join(ROOT, "tests", "golden")
+# tables the GPU tests write for a reader (per-parameter gradient errors, parity reports, a hung rank's stacks); git-ignored
+DIAG_DIR = os.path.join(ROOT, "test_diagnostics")
 
 
 def pytest_configure(config):
@@ -16,6 +18,12 @@ def pytest_configure(config):
 @pytest.fixture(scope="session")
 def golden_dir():
     return GOLDEN
+
+
+def diag_path(name):
+    """DIAG_DIR/``name``; creates DIAG_DIR, which a fresh checkout does not have"""
+    os.makedirs(DIAG_DIR, exist_ok=True)
+    return os.path.join(DIAG_DIR, name)
 
 
 def load_golden(name):

@@ -200,3 +200,53 @@ def test_committed_final_detail_holds_parity_within_the_stated_tolerances():
     assert abs(j["parity"]["min_cosine"] - min(db["grad_min_cosine"], b["grad_min_cosine"], 1.0)) < 2e-3
     # the compact line IS bench.compact_line of the detail file
     assert json.loads(bench.compact_line(d, j.get("detail"))) == j
+
+
+# ----------------------------------------------------------------------------------------------- --dump-outputs
+def test_dump_outputs_names_every_returned_array_and_keeps_the_budget(tmp_path):
+    """bench.named_arrays flattens what a step returns (dicts, lists, Act views: their real channels only); bench.dump_outputs writes
+    float32 / float64 .npy files under the byte budget -- small arrays whole, large ones cut to the same seeded positions every time."""
+    import numpy as np
+    import torch
+    import hr_viton_amd  # noqa: F401
+    from hr_viton_amd.ops import Act
+    g = torch.Generator().manual_seed(0)
+    ret = {"output": torch.randn(2, 3, 64, 48, generator=g), "flow_list": [torch.randn(1, 8, 6, 2, generator=g)],
+           "parse": Act(torch.arange(2 * 4 * 3 * 8, dtype=torch.float32).reshape(2, 4, 3, 8).to(torch.bfloat16), 7),
+           "labels": torch.randint(0, 13, (2, 64, 48), generator=g), "loss": {"GAN": torch.tensor(1.5)},
+           "params": torch.randn(200_000, generator=g, dtype=torch.float64)}
+    arrays = bench.named_arrays(ret)
+    assert {k: tuple(v.shape) for k, v in arrays.items()} == {
+        "output": (2, 3, 64, 48), "flow_list_0": (1, 8, 6, 2), "parse": (2, 4, 3, 7), "labels": (2, 64, 48), "loss_GAN": (), "params": (200_000,)}
+    whole = bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    assert all(s == list(arrays[k].shape) for k, s in whole.items())
+    p = np.load(tmp_path / "whole" / "parse.npy")
+    assert p.dtype == np.float32 and np.array_equal(p, ret["parse"].t[..., :7].float().numpy())
+    assert np.load(tmp_path / "whole" / "params.npy").dtype == np.float64 and np.load(tmp_path / "whole" / "labels.npy").dtype == np.float32
+
+    limit = 600_000
+    for run in ("a", "b"):
+        cut = bench.dump_outputs(str(tmp_path / run), arrays, limit=limit)
+        assert sum(os.path.getsize(tmp_path / run / f) for f in os.listdir(tmp_path / run)) <= limit
+    assert {k: s for k, s in cut.items() if k != "params"} == {k: s for k, s in whole.items() if k != "params"}   # the small ones whole
+    assert len(cut["params"]) == 1 and 50_000 < cut["params"][0] < 200_000       # the large one fills the rest of the budget
+    full = arrays["params"].numpy()
+    for k in cut:
+        a, b = np.load(tmp_path / "a" / f"{k}.npy"), np.load(tmp_path / "b" / f"{k}.npy")
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), k
+    assert np.isin(np.load(tmp_path / "a" / "params.npy"), full).all()       # a sample of the array's own elements
+
+
+def test_a_read_only_checkout_still_gets_the_line(tmp_path, monkeypatch):
+    """bench.py run from a tree it cannot write to: the side files (detail JSON, parity tables) are skipped, the line still goes out"""
+    blocked = tmp_path / "file"
+    blocked.write_text("")
+    assert bench.writable_dir(str(blocked / "sub")) is None           # cannot be created (its parent is a file)
+    assert bench.writable_dir(str(tmp_path / "a" / "b")) == str(tmp_path / "a" / "b") and (tmp_path / "a" / "b").is_dir()
+    monkeypatch.setattr(bench, "ROOT", str(blocked))
+    buf = io.StringIO()
+    with contextlib.redirect_stdout(buf):
+        bench.emit(_full())
+    lines = buf.getvalue().splitlines()
+    j = json.loads(lines[0])
+    assert len(lines) == 1 and "detail" not in j and j["ms_per_step"] == 74.0 and all(k in j for k in CONTRACT)

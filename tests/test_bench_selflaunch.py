@@ -47,3 +47,20 @@ def test_launched_by_torch_distributed_run_it_does_not_relaunch():
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1 and json.loads(lines[0])["n_gpus"] == 2
+
+
+def test_dump_outputs_writes_the_last_step_and_repeats_run_to_run(tmp_path):
+    # --dump-outputs: what the timed path returned in its last step, as DIR/<name>.npy; the inputs are seeded, so a second run
+    # with the same arguments writes the same arrays
+    import numpy as np
+    for d in ("a", "b"):
+        r = _run(["--gpus", "1", "--workload", "stub", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / d)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])["steps"] == 3
+    a, b = np.load(tmp_path / "a" / "y.npy"), np.load(tmp_path / "b" / "y.npy")
+    assert os.listdir(tmp_path / "a") == ["y.npy"] and a.dtype == np.float32 and a.shape == (1,) and np.array_equal(a, b)
+
+
+def test_steps_below_one_is_refused():
+    r = _run(["--gpus", "1", "--workload", "stub", "--steps", "0"])
+    assert r.returncode != 0 and "--steps" in r.stderr

@@ -10,6 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from conftest import diag_path
 from oracle import hrviton_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -229,9 +230,7 @@ def _compare_grads(mod, sd, tol, what):
         aerr = (p.grad.detach().cpu() - want).abs().max().item()
         rows.append((aerr / max(want.abs().max().item(), 1e-3 * gmax), aerr, want.abs().max().item(), name))
     rows.sort(reverse=True)
-    d = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out")
-    os.makedirs(d, exist_ok=True)
-    with open(os.path.join(d, "grad_diag_" + what.split()[0] + ".txt"), "w") as f:
+    with open(diag_path("grad_diag_" + what.split()[0] + ".txt"), "w") as f:
         f.write(f"# {what}: rel_err abs_err |want|max name   (global max grad {gmax:.3e})\n")
         for r in rows:
             f.write("%.3e %.3e %.3e %s\n" % r)
@@ -457,8 +456,8 @@ def test_three_training_iterations_against_the_oracle():
             assert abs(float(losses[k].detach()) - float(r[k].detach())) < 1e-4 * max(1.0, abs(float(r[k].detach()))), (it, k)
         gmax = max(v.abs().max().item() for v in want_g.values())
         errs = sorted(((cap[k] - w).abs().max().item() / max(w.abs().max().item(), 1e-3 * gmax), k) for k, w in want_g.items())
-        os.makedirs("gpurun_out", exist_ok=True)
-        with open("gpurun_out/grad_diag_tocg_3iter.txt", "a" if it else "w") as f:
+        diag = diag_path("grad_diag_tocg_3iter.txt")
+        with open(diag, "a" if it else "w") as f:
             f.write(f"# iteration {it}: relative gradient error (max-abs / max|want|), worst 8 of {len(errs)}; median "
                     f"{errs[len(errs) // 2][0]:.2e}\n" + "".join(f"{e:.3e} {k}\n" for e, k in errs[-8:]))
         # The gradient of this loss is a DISCONTINUOUS function of the forward values: sign() of the L1 / TV terms,
@@ -481,7 +480,7 @@ def test_three_training_iterations_against_the_oracle():
             ep = sorted((sd_p[k].grad - w).abs().max().item() / max(w.abs().max().item(), 1e-3 * gmax)
                         for k, w in want_g.items())
             cal_med, cal_worst = max(cal_med, ep[len(ep) // 2]), max(cal_worst, ep[-1])
-        with open("gpurun_out/grad_diag_tocg_3iter.txt", "a") as f:
+        with open(diag, "a") as f:
             f.write(f"# iteration {it}: oracle under 1e-5 input perturbations: median {cal_med:.2e} worst {cal_worst:.2e}\n")
         assert errs[len(errs) // 2][0] < 2 * cal_med + 1e-4, (it, errs[len(errs) // 2], cal_med)
         assert errs[-1][0] < 2 * cal_worst + 1e-3, (it, errs[-1], cal_worst)

@@ -22,10 +22,10 @@ def _free_port():
 
 
 def _watchdog(tag, rank):
-    """a hung rank writes its Python stacks to gpurun_out/ instead of dying silently with the parent's timeout"""
+    """a hung rank writes its Python stacks to test_diagnostics/ instead of dying silently with the parent's timeout"""
     import faulthandler
-    os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-    f = open(os.path.join(ROOT, "gpurun_out", f"dp_{tag}_rank{rank}_stacks.txt"), "w")
+    from conftest import diag_path
+    f = open(diag_path(f"dp_{tag}_rank{rank}_stacks.txt"), "w")
     faulthandler.dump_traceback_later(90, repeat=False, file=f, exit=False)
     return f
 

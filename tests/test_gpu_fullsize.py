@@ -5,7 +5,7 @@ uses: 1040/528/272-channel gamma|beta convolutions, 64-column patch tiles, sub-b
   (stated fp32 tolerance 1e-3 rel, north star) and bf16 engine vs the oracle with the same rounding points
   (oracle.QUANT) -- one CPU forward each (~10 s).
 * The generator half of one train_generator.py iteration (:279-322) at 512x384 ngf=64 vs torch autograd over the
-  oracle: image, loss terms incl. VGG, every parameter gradient (table -> gpurun_out/).
+  oracle: image, loss terms incl. VGG, every parameter gradient (table -> test_diagnostics/).
 """
 import os
 from argparse import Namespace
@@ -13,13 +13,13 @@ from argparse import Namespace
 import pytest
 import torch
 
+from conftest import DIAG_DIR
 from oracle import hrviton_oracle as O
 from oracle import step_check
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OUT = os.path.join(ROOT, "gpurun_out")
+OUT = DIAG_DIR
 
 
 def _gen(fp16):

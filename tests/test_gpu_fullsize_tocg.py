@@ -12,10 +12,11 @@ from argparse import Namespace
 import pytest
 import torch
 
+from conftest import DIAG_DIR
 from oracle import hrviton_oracle as O
 
 pytestmark = pytest.mark.gpu
-OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out")
+OUT = DIAG_DIR
 
 
 def test_tocg_bf16_engine_1024x768_ngf96_vs_quant_oracle():

@@ -8,7 +8,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from conftest import load_golden
+from conftest import diag_path, load_golden
 from oracle import hrviton_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -203,7 +203,7 @@ def test_bf16_serving_paths_agree_at_full_size(monkeypatch):
     conv_0 / conv_1 / conv_img / conv_7 of the fine levels on conv_p2.hip / thin_conv.hip -- against the same plan with each of
     those switched off (HRV_XUP=0, HRV_SERVE_FAST=0, HRV_SPADE_FUSED=0: the round-3 route).  Same bf16 operand rounding
     everywhere, different accumulation orders: two routes differ by less (mean abs) than either differs from the fp32 engine, and
-    all sit equally far from it (within 15 %; numbers in gpurun_out/serving_paths_1024x768.txt)."""
+    all sit equally far from it (within 15 %; numbers in test_diagnostics/serving_paths_1024x768.txt)."""
     import hr_viton_amd  # noqa: F401
     from hr_viton_amd.network_generator import SPADEGenerator
     opt = Namespace(cuda=True, norm_G="spectralaliasinstance", gen_semantic_nc=7, ngf=64, num_upsampling_layers="most",
@@ -243,7 +243,7 @@ def test_bf16_serving_paths_agree_at_full_size(monkeypatch):
     for k, o in outs.items():
         rows.append(f"{k}: vs default mean {float((o - ref).abs().mean()):.3e} max {float((o - ref).abs().max()):.3e}; "
                     f"vs fp32 engine mean {float((o - fp).abs().mean()):.3e}")
-    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out", "serving_paths_1024x768.txt"), "w") as f:
+    with open(diag_path("serving_paths_1024x768.txt"), "w") as f:
         f.write("\n".join(rows) + "\n")
     for k, o in outs.items():
         # two bf16 routes differ by less than either differs from the fp32 engine
@@ -300,7 +300,7 @@ def test_generator_bf16_engine_matches_bf16_emulation():
         O.QUANT["fn"] = None
     err = (out_bf - want_bf).abs()
     dev = (out_bf - want_fp).abs()
-    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out", "bf16_gen_err.txt"), "w") as f:
+    with open(diag_path("bf16_gen_err.txt"), "w") as f:
         f.write(f"vs bf16 emulation: max {err.max().item()} mean {err.mean().item()} frac>0.05 {(err > 0.05).float().mean().item()}\n")
         f.write(f"vs fp32 oracle:    max {dev.max().item()} mean {dev.mean().item()} frac>0.05 {(dev > 0.05).float().mean().item()}\n")
     assert err.mean() < 5e-3 and (err > 5e-2).float().mean() < 3e-2, (err.max().item(), err.mean().item())

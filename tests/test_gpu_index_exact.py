@@ -8,20 +8,18 @@
   order differs between ANY two implementations (the reference's own CPU result depends on oneDNN's blocking and the
   thread count): a mismatching pixel is legal only where the oracle's top-2 margin is within a stated number of ulps
   of the winning logit.  The trained-like regime (ReLU logits, 1024x768) is run here and the margins are written to
-  gpurun_out/argmax_margins.txt.
+  test_diagnostics/argmax_margins.txt.
 """
-import os
 from argparse import Namespace
 
 import pytest
 import torch
 import torch.nn as nn
 
+from conftest import diag_path
 from oracle import hrviton_oracle as O
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _merge_onehot(lab, H, W):
@@ -127,8 +125,7 @@ def test_trained_like_regime_1024x768_margins_in_ulps():
         checks.append((bad.sum().item() <= max_px and (u.numel() == 0 or float(u.max()) <= bound), lines[-1]))
         lines.append(f"   exact top-2 ties after the blur (first-max rule decides there): "
                      f"{float((top2[:, 0] == top2[:, 1]).float().mean()):.2e} of the pixels")
-    os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-    with open(os.path.join(ROOT, "gpurun_out", "argmax_margins.txt"), "w") as f:
+    with open(diag_path("argmax_margins.txt"), "w") as f:
         f.write("\n".join(lines) + "\n")
     for ok, msg in checks:
         assert ok, msg

@@ -9,11 +9,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from conftest import DIAG_DIR
 from oracle import hrviton_oracle as O
 
 pytestmark = pytest.mark.gpu
 
-DIAG_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out")
 
 
 def _ops():
@@ -407,8 +407,8 @@ def test_conv_bf16_patch_mode(case):
     assert (outs[8] - outs[17]).abs().max() <= 2 ** -7 * ref.abs().max()
     assert (outs[8] - outs[18]).abs().max() <= 2 ** -7 * ref.abs().max()
     d = (outs[8] - outs[16]).abs()
-    os.makedirs("gpurun_out", exist_ok=True)
-    with open("gpurun_out/patch_mode_diff.txt", "a") as f:
+    os.makedirs(DIAG_DIR, exist_ok=True)
+    with open(os.path.join(DIAG_DIR, "patch_mode_diff.txt"), "a") as f:
         f.write(f"{name}: max|cfg8-cfg16|={d.max().item():.3e} differing={int((d > 0).sum())}/{d.numel()} "
                 f"max|ref|={ref.abs().max().item():.3f}\n")
     assert d.max() <= 2 ** -7 * ref.abs().max()

@@ -7,6 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from conftest import diag_path
 from oracle import hrviton_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -70,9 +71,7 @@ def _compare_grads(mod, sd, tol, what):
         aerr = (p.grad.detach().cpu() - want).abs().max().item()
         rows.append((aerr / max(want.abs().max().item(), 1e-3 * gmax), aerr, want.abs().max().item(), name))
     rows.sort(reverse=True)
-    d = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out")
-    os.makedirs(d, exist_ok=True)
-    with open(os.path.join(d, "grad_diag_" + what.split()[0] + ".txt"), "w") as f:
+    with open(diag_path("grad_diag_" + what.split()[0] + ".txt"), "w") as f:
         f.write(f"# {what}: rel_err abs_err |want|max name   (global max grad {gmax:.3e})\n")
         for r in rows:
             f.write("%.3e %.3e %.3e %s\n" % r)
@@ -241,11 +240,9 @@ def test_mixed_precision_generator_step_against_the_oracle():
     cosine, within the stated bf16 tolerance (operands carry 8 mantissa bits)."""
     import os
     from oracle import step_check
-    out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out")
-    os.makedirs(out, exist_ok=True)
     rep = step_check.compare_generator_step(256, 128, 16, 16, 2, seed=5, mixed=(False, True), cpu_threads=min(os.cpu_count() or 1, 16),
-                                            table_path=os.path.join(out, "grad_parity_gen_256x128_ngf16.txt"))
-    with open(os.path.join(out, "step_parity_gen_256x128_ngf16.txt"), "w") as f:
+                                            table_path=diag_path("grad_parity_gen_256x128_ngf16.txt"))
+    with open(diag_path("step_parity_gen_256x128_ngf16.txt"), "w") as f:
         f.write(repr(rep) + "\n")
     f32, b16 = rep[False], rep[True]
     assert f32["image_max_rel_err"] < 1e-3 and all(v < 1e-3 for v in f32["loss_rel_err"].values()) and f32["grad_worst_rel_err"] < 2e-2, f32
