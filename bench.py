@@ -8,9 +8,12 @@ VGG19 + feature-matching + hinge losses, fused Adam on both networks; DP all-red
 A "step" is that whole iteration over one synthetic batch already resident in HBM.  N>1: one process per GPU
 (torch.distributed.run, backend nccl = RCCL), weak scaling; value = images of all ranks / max-over-ranks time.
 
-Output: the LAST stdout line is ONE compact JSON object under 4 KB (compact_line): the contract keys, `roofline`, `cpu_baseline`, the
-worst `parity` numbers, value / ms / frac of the `extra` configurations.  The full result -- every table, note and sub-object below --
-is written to gpurun_out/bench_detail.json (the line's `detail` key names it); progress goes to stderr.
+Output: the LAST stdout line is ONE compact JSON object under 4 KB (compact_line); progress goes to stderr.  A plain run does only
+what its headline figure needs: set-up, --warmup W untimed and --steps K timed steps, the --dump-outputs arrays, the line -- the
+contract keys, with `roofline`, `cpu_baseline` and `parity` null.  --full adds, after the timed steps, everything else the benchmark
+measures and checks (one profiled step for `roofline`, then `cpu_baseline`, `parity`, `extra`; --no-cpu-baseline / --no-extras leave
+parts of it out), puts their worst numbers on the line and writes the full result -- every table, note and sub-object below -- to
+bench_detail.json in the run's output folder (the line's `detail` key names the file).  --dump-launches runs the profiled step too.
   roofline     -- the DOMINANT kernel of the step: the device-kernel family with the largest summed HIP-event time in one iteration
                   (template instances of one kernel summed -- what heads a rocprofv3 kernel trace of the same command), its
                   algorithmic FLOPs / that time against the 2.5 PFLOP/s dense bf16 MFMA peak (an HBM-bound family: bytes against
@@ -496,17 +499,20 @@ def timed_region(ctx, wl, steps, warmup, device_sync, dump_dir=None):
     return dt
 
 
-def measure(ctx, wl, steps, warmup, mixed, dump=None, dump_dir=None):
-    """Timed region (driver contract) + one extra profiled step with per-launch HIP events."""
+def measure(ctx, wl, steps, warmup, mixed, dump=None, dump_dir=None, profile=True):
+    """Timed region (driver contract) + (``profile``) one extra profiled step with per-launch HIP events; without it
+    ``summary`` is None."""
     torch, ops = ctx["torch"], ctx["ops"]
     dt = timed_region(ctx, wl, steps, warmup, torch.cuda.synchronize, dump_dir)
-    ops.profile_begin()
-    wl["step"](0)
-    recs = ops.profile_end(kernels=True)
-    if dump and ctx["rank"] == 0:
-        dump_launches(dump, recs)
     peak = PEAK_BF16_MFMA_TFLOPS if mixed else PEAK_F32_MFMA_TFLOPS
-    s = summarize(recs, peak)
+    s = None
+    if profile:
+        ops.profile_begin()
+        wl["step"](0)
+        recs = ops.profile_end(kernels=True)
+        if dump and ctx["rank"] == 0:
+            dump_launches(dump, recs)
+        s = summarize(recs, peak)
     B, world = wl["B"], ctx["world"]
     res = {"value": round(B * world * steps / dt, 3), "ms_per_step": round(dt / steps * 1e3, 3), "peak": peak,
            "summary": s, "dt": dt}
@@ -758,15 +764,20 @@ def wl_stub(ctx, B):
                 workload="stub: CPU matmul + all-reduce", traffic_tag="stub")
 
 
-def main():
+def make_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU legs (cpu_baseline, parity)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the configs[4] / configs[1] sub-measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beyond the headline figure: one profiled step "
+                         "(roofline), the CPU baseline, parity against the oracle, the other BASELINE configurations (extra); "
+                         "writes the detail file")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU legs (cpu_baseline, parity)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the configs[4] / configs[1] / configs[2] sub-measurements")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads for the CPU legs (0 = min(cores, 32))")
-    ap.add_argument("--dump-launches", default=None, help="write the per-launch table of one step to this file")
+    ap.add_argument("--dump-launches", default=None, help="run one profiled step after the timed ones (its roofline goes on the line) and "
+                                                          "write its per-launch table to this file")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="write what the timed path returned in its last timed step (a training workload: also the updated weights) "
                          "as DIR/<name>.npy, float32 or float64, at most 64 MB in all (larger arrays: a fixed seeded sample); the "
@@ -783,6 +794,21 @@ def main():
                          "RCCL's collectives under data parallelism.  Default: HRV_RESERVE_CUS or 0")
     ap.add_argument("--graph", action="store_true", help="tryon_infer / train_generator: replay the step as one captured hipGraph (train_generator on N > 1 GPUs: graph "
                          "segments with the gradient all-reduces between them)")
+    return ap
+
+
+def planned_legs(args, rank, world):
+    """What a GPU run does after its timed steps (and the --dump-outputs arrays).  A plain run: nothing -- its line is the headline
+    figure alone.  --full: the profiled step, the CPU legs and the extra configurations (one process, rank 0), the detail file."""
+    single = rank == 0 and world == 1 and args.full
+    return {"profiled_step": bool(args.full or args.dump_launches),
+            "cpu_legs": single and not args.no_cpu_baseline,
+            "extras": single and not args.no_extras and args.workload == "train_generator",
+            "detail_file": bool(args.full)}
+
+
+def main():
+    ap = make_parser()
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
@@ -828,8 +854,9 @@ def main():
 
     _log(f"building workload {args.workload} ({'bf16' if mixed else 'fp32'})")
     wl = make_workload(ctx, args.workload, mixed, args.batch)
+    legs = planned_legs(args, rank, world)
     _log("timed region")
-    res = measure(ctx, wl, args.steps, args.warmup, mixed, args.dump_launches, args.dump_outputs)
+    res = measure(ctx, wl, args.steps, args.warmup, mixed, args.dump_launches, args.dump_outputs, profile=legs["profiled_step"])
     _log(f"{res['value']} images/s, {res['ms_per_step']} ms/step")
     res["steps"] = args.steps
     s = res["summary"]
@@ -845,10 +872,10 @@ def main():
                            "parallelism": f"dp{world}" + ("-allreduce" if wl["train"] else "-replicas"),
                            "persistent_grid_cus": int(ops._lib.load().hrv_persistent_cus()),
                            **dist_fields(tdist)},
-                "roofline": roofline_obj(wl, res, north_star=(args.workload in ("train_generator", "tryon_infer"))),
-                "per_kind_ms": {k: {"launches": v[0], "ms": round(v[1], 2)} for k, v in sorted(s["kinds"].items())},
+                "roofline": roofline_obj(wl, res, north_star=(args.workload in ("train_generator", "tryon_infer"))) if s else None,
+                "per_kind_ms": {k: {"launches": v[0], "ms": round(v[1], 2)} for k, v in sorted(s["kinds"].items())} if s else None,
                 "cpu_baseline": None, "parity": None}
-    cpu_legs = rank == 0 and world == 1 and not args.no_cpu_baseline
+    cpu_legs = legs["cpu_legs"]
     if cpu_legs:
         torch.set_num_threads(ctx["cpu_threads"])
         if wl.get("cpu_baseline"):
@@ -857,7 +884,7 @@ def main():
         if wl.get("parity"):
             _log("parity leg")
             line["parity"] = wl["parity"]()
-    if rank == 0 and world == 1 and not args.no_extras and args.workload == "train_generator":
+    if legs["extras"]:
         # the other two measured configurations of BASELINE.json, same process, after the headline's timed region
         extra = {}
         del wl
@@ -894,7 +921,10 @@ def main():
         line["cpu_baseline"] = {"value": round(1.0 / p["oracle_forward_s"], 4), "unit": "images/s", "cores": ctx["cpu_threads"],
                                 "kind": "port", "sample": "1 image 1024x768, one forward of oracle.tocg_forward"}
     if rank == 0:
-        emit(line)
+        if legs["detail_file"]:
+            emit(line)
+        else:
+            print(compact_line(line), flush=True)
     if tdist.is_available() and tdist.is_initialized():
         tdist.barrier()
         tdist.destroy_process_group()

@@ -250,3 +250,39 @@ def test_a_read_only_checkout_still_gets_the_line(tmp_path, monkeypatch):
     lines = buf.getvalue().splitlines()
     j = json.loads(lines[0])
     assert len(lines) == 1 and "detail" not in j and j["ms_per_step"] == 74.0 and all(k in j for k in CONTRACT)
+
+
+# ----------------------------------------------------------------------------------------------- plain run / --full
+def test_a_plain_run_does_only_the_headline_and_full_does_the_rest():
+    """``bench.py --gpus 1 --steps K --warmup W`` stops after the timed steps; the profiled step, the CPU legs, the extra
+    configurations and the detail file are --full's, trimmed there by --no-cpu-baseline / --no-extras as before."""
+    p = bench.make_parser()
+
+    def legs(argv, rank=0, world=1):
+        return bench.planned_legs(p.parse_args(argv), rank, world)
+    assert legs(["--gpus", "1", "--steps", "20", "--warmup", "5"]) == {
+        "profiled_step": False, "cpu_legs": False, "extras": False, "detail_file": False}
+    assert not any(legs(["--workload", "tocg_infer", "--no-cpu-baseline", "--no-extras"]).values())
+    assert not any(legs(["--dump-outputs", "out"]).values())
+    assert all(legs(["--full"]).values())
+    assert legs(["--full", "--no-cpu-baseline"]) == {"profiled_step": True, "cpu_legs": False, "extras": True, "detail_file": True}
+    assert legs(["--full", "--no-cpu-baseline", "--no-extras"]) == {
+        "profiled_step": True, "cpu_legs": False, "extras": False, "detail_file": True}
+    assert legs(["--full", "--workload", "tocg_infer"])["extras"] is False and legs(["--full", "--workload", "tocg_infer"])["cpu_legs"]
+    # N > 1: every rank takes the profiled step (its collectives), no rank the CPU legs or the extras
+    for rank in (0, 1):
+        assert legs(["--full", "--gpus", "2"], rank, 2) == {"profiled_step": True, "cpu_legs": False, "extras": False, "detail_file": True}
+    # --dump-launches asks for the profiled step by itself
+    assert legs(["--dump-launches", "l.txt"]) == {"profiled_step": True, "cpu_legs": False, "extras": False, "detail_file": False}
+
+
+def test_a_plain_run_line_carries_the_contract_keys_with_the_extra_measurements_null():
+    full = _full()
+    line = {k: v for k, v in full.items() if k not in ("extra", "per_kind_ms")}
+    line.update(roofline=None, cpu_baseline=None, parity=None)
+    j = json.loads(bench.compact_line(line))
+    for k in CONTRACT:
+        assert k in j, k
+    assert j["roofline"] is None and j["cpu_baseline"] is None and j["parity"] is None and "extra" not in j and "detail" not in j
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert j[k] == full[k], k

@@ -10,7 +10,7 @@ for R in 0 18 72; do
     | tee -a $OUT/overlap.txt
 done
 cd /tmp && export TMPDIR=/tmp
-HRV_FAKE_ALLREDUCE=18 timeout 400 rocprofv3 --kernel-trace -d $OUT/trace -o trace -- python $REPO/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras > $OUT/trace.log 2>&1
+HRV_FAKE_ALLREDUCE=18 timeout 400 rocprofv3 --kernel-trace -d $OUT/trace -o trace -- python $REPO/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extras > $OUT/trace.log 2>&1
 f=$(ls $OUT/trace/*.db 2>/dev/null | head -1)
 [ -n "$f" ] && (cd $REPO && python tools/dp_overlap.py $f | tee -a $OUT/overlap.txt)
 rm -rf $OUT/trace

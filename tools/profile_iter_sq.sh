@@ -1,6 +1,6 @@
 #!/bin/bash
 # SQ counters of EVERY kernel of the headline iteration (not a micro-benchmark): one PMC pass (own run, kernel-trace only) over
-# `python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-extras` -- matrix-pipe busy cycles per kernel name next to the kernel's
+# `python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-extras` -- matrix-pipe busy cycles per kernel name next to the kernel's
 # wave cycles, so the dominant kernel's MFMA utilisation is the one it has INSIDE the iteration.  Run via gpurun from the repo root;
 # writes gpurun_out/pmc_iter/sq1.summary.txt and mfma_busy_per_kernel.txt.
 set -u
@@ -8,7 +8,7 @@ REPO=$(pwd); OUT=$REPO/gpurun_out/pmc_iter; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 timeout 400 rocprofv3 --kernel-trace \
   --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_MFMA GRBM_GUI_ACTIVE \
-  -d $OUT/sq1 -o sq1 -- python $REPO/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-extras > $OUT/sq1.log 2>&1
+  -d $OUT/sq1 -o sq1 -- python $REPO/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-extras > $OUT/sq1.log 2>&1
 cd $REPO
 f=$(ls $OUT/sq1/*.db 2>/dev/null | head -1)
 [ -n "$f" ] && python tools/rocprof_summary.py $f > $OUT/sq1.summary.txt 2>&1

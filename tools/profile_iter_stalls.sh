@@ -6,7 +6,7 @@
 # HRV_STALL_CMD overrides the profiled command (e.g. a micro-benchmark).
 set -u
 REPO=$(pwd); OUT=$REPO/gpurun_out/pmc_stalls; mkdir -p $OUT
-CMD=${HRV_STALL_CMD:-"python $REPO/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-extras"}
+CMD=${HRV_STALL_CMD:-"python $REPO/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-extras"}
 cd /tmp && export TMPDIR=/tmp
 timeout 400 rocprofv3 --kernel-trace \
   --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_LDS_ADDR_CONFLICT SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE \

@@ -56,7 +56,7 @@ PY
 echo "best reserve setting at N=$NGPU: $R CUs" | tee -a $OUT/best.txt
 cd /tmp && export TMPDIR=/tmp
 N=$((NGPU < 8 ? NGPU : 8))
-timeout 900 rocprofv3 --kernel-trace -d $OUT/trace -o trace -- python $REPO/bench.py --gpus $N --steps 3 --warmup 2 --reserve-cus $R \
+timeout 900 rocprofv3 --kernel-trace -d $OUT/trace -o trace -- python $REPO/bench.py --full --gpus $N --steps 3 --warmup 2 --reserve-cus $R \
   --no-cpu-baseline --no-extras > $OUT/trace.log 2>&1
 cd $REPO
 i=0
