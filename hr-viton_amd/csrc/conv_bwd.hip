@@ -974,6 +974,7 @@ int wgrad_s2_try(const void* dy, int dy_cs, int dy_co, int Cout, const void* x, 
                  int CinTot, int N, int H, int W, int Ho, int Wo, float* workspace, long long workspace_bytes, float* dbias, hipStream_t st,
                  int* S_out);
 int wgrad_s2_serves(int Cout, int x_C, int x_cs, int x_co, int dy_cs, int dy_co, int N, int H, int W);
+int wgrad_tr_serves(int dy_cs, int dy_co, int Cout, int x_C, int x_cs, int x_co, int N, int H, int W, int KH, int KW, int pad);
 }
 
 static int wgrad_impl(const float* dy, int32_t dy_cstride, int32_t dy_coff, int32_t Cout, const float* x, int32_t x_C,
@@ -997,6 +998,9 @@ static int wgrad_impl(const float* dy, int32_t dy_cstride, int32_t dy_coff, int3
   p.x_bf16 = x_bf16 ? 1 : 0;
   HRV_REQUIRE(!(x_bf16 || dy_bf16) || mma_bf16, "wgrad: bf16-stored operands exist for the bf16 matrix-core kernel only");
   HRV_REQUIRE(!dy_bf16 || x_bf16, "wgrad: storage_flags 1 (bf16 dY with fp32 X) is not built");
+  // The conditions in front of the two tries below are repeated by train_ops.conv_wgrad, which asks hrv_conv2d_wgrad_{tr,s2}_supported
+  // under the same conditions to know which kernel will run (it pads a bf16 dY to a multiple of 4 columns for the generic kernel
+  // otherwise, and labels its launch record): edit both places together.
   if (mma_bf16 && x_bf16 && dy_bf16 && stride == 1 && Ho == H && Wo == W && x_up_shift == 0) {
     int S2 = 0;
     const int r = wgrad_tr_try(dy, dy_cstride, dy_coff, Cout, x, x_C, x_cstride, x_coff, x_C_real, ci_base, CinTot, N, H, W,
@@ -1132,4 +1136,9 @@ extern "C" int hrv_colsum_nhwc_f32(const float* x, int64_t P, int32_t C, int32_t
 extern "C" int hrv_conv2d_wgrad_s2_supported(int32_t Cout, int32_t x_C, int32_t x_cstride, int32_t x_coff, int32_t dy_cstride, int32_t dy_coff,
                                              int32_t N, int32_t H, int32_t W) {
   return hrv::wgrad_s2_serves(Cout, x_C, x_cstride, x_coff, dy_cstride, dy_coff, N, H, W);
+}
+
+extern "C" int hrv_conv2d_wgrad_tr_supported(int32_t Cout, int32_t x_C, int32_t x_cstride, int32_t x_coff, int32_t dy_cstride, int32_t dy_coff,
+                                             int32_t N, int32_t H, int32_t W, int32_t KH, int32_t KW, int32_t pad) {
+  return hrv::wgrad_tr_serves(dy_cstride, dy_coff, Cout, x_C, x_cstride, x_coff, N, H, W, KH, KW, pad);
 }

@@ -310,20 +310,43 @@ __global__ __launch_bounds__(256) void conv_wgrad_s2_kernel(const WgradS2Params 
   }
 }
 
-// 1 / 2: the shape class the kernel serves (the conditions wgrad_s2_try applies), 0: none
-static int wgrad_s2_class(int Cout, int x_C, int x_cs, int x_co, int dy_cs, int dy_co, int N, int H, int W) {
+// The slab count of a shape class (tm: 32-cout tiles per block) and whether every slab's extent fits the kernel's 31-bit scalar offsets
+static bool wgrad_s2_slabs(int tm, int Cout, int x_cs, int dy_cs, int N, int H, int W, int& S) {
+  const int Ho = H / 2 + 1, Wo = W / 2 + 1;
+  const int tiles_per_row = (Wo + 63) / 64;
+  const int n_tiles = N * Ho * tiles_per_row;
+  const int jobs = Cout / (32 * tm) * 4;
+  // one block per CU (a block owns 120-150 KB of LDS): the grid must not exceed the CU count
+  const int n_cu = persistent_cus();
+  S = n_cu / jobs;
+  if (S > n_tiles / 8) S = n_tiles / 8;
+  if (S > 256) S = 256;
+  if (S < 1) S = 1;
+  // per-tile scalar offsets are relative to the slab's first row: the slab's extent must fit 31 bits
+  const long long slab_rows = (long long)n_tiles / S / tiles_per_row + 4;
+  return !((2 * slab_rows + 8) * W * (long long)x_cs * 2 >= 0x7FF00000LL || slab_rows * Wo * (long long)dy_cs * 2 >= 0x7FF00000LL);
+}
+
+// 1 / 2: the shape class the kernel serves (EVERY condition wgrad_s2_try applies before it launches: hrv_conv2d_wgrad_s2_supported
+// answers from it, and its caller pads a bf16 dY for the fallback kernel when the answer is no), 0: none.  S: the class's slab count
+static int wgrad_s2_class(int Cout, int x_C, int x_cs, int x_co, int dy_cs, int dy_co, int N, int H, int W, int& S) {
   const char* env = hrv::env("HRV_WGRAD_S2");
   if (env && env[0] == '0') return 0;
+  if (Cout < 1 || x_C < 1 || N < 1 || H < 1 || W < 1) return 0;
   if ((dy_cs | dy_co | x_cs | x_co | x_C) & 7) return 0;                         // 16-byte DMA granules
   const int Ho = H / 2 + 1, Wo = W / 2 + 1;
   if ((long long)N * Ho * Wo < 8192 || Wo < 32) return 0;
   const int gpt = (x_C + 31) / 32;
-  if (gpt == 2 && Cout % 128 == 0) return 1;            // 64 -> 128 (model1): 128 couts x (4 kw x 2 chunks)
-  if (gpt == 4 && Cout % 64 == 0) return 2;             // 128 -> 256 (model2): 64 couts x (4 kw x 4 chunks)
-  return 0;
+  int c_ = 0;
+  S = 0;
+  if (gpt == 2 && Cout % 128 == 0) c_ = 1;              // 64 -> 128 (model1): 128 couts x (4 kw x 2 chunks)
+  else if (gpt == 4 && Cout % 64 == 0) c_ = 2;          // 128 -> 256 (model2): 64 couts x (4 kw x 4 chunks)
+  if (c_ == 0 || !wgrad_s2_slabs(c_ == 1 ? 4 : 2, Cout, x_cs, dy_cs, N, H, W, S)) return 0;
+  return c_;
 }
 int wgrad_s2_serves(int Cout, int x_C, int x_cs, int x_co, int dy_cs, int dy_co, int N, int H, int W) {
-  return wgrad_s2_class(Cout, x_C, x_cs, x_co, dy_cs, dy_co, N, H, W) != 0 ? 1 : 0;
+  int S = 0;
+  return wgrad_s2_class(Cout, x_C, x_cs, x_co, dy_cs, dy_co, N, H, W, S) != 0 ? 1 : 0;
 }
 
 // Host side.  Returns 1 when the kernel was launched (partials in `workspace`, *S_out slabs), 0 when the shape is not one it
@@ -332,7 +355,8 @@ int wgrad_s2_try(const void* dy, int dy_cs, int dy_co, int Cout, const void* x, 
                  int CinTot, int N, int H, int W, int Ho, int Wo, float* workspace, long long workspace_bytes, float* dbias, hipStream_t st,
                  int* S_out) {
   if (Ho != H / 2 + 1 || Wo != W / 2 + 1) return 0;
-  const int c_ = wgrad_s2_class(Cout, x_C, x_cs, x_co, dy_cs, dy_co, N, H, W);
+  int S = 0;
+  const int c_ = wgrad_s2_class(Cout, x_C, x_cs, x_co, dy_cs, dy_co, N, H, W, S);
   if (c_ == 0) return 0;
   const int cls = c_ - 1, tm = c_ == 1 ? 4 : 2;
   const int gpt = (x_C + 31) / 32;
@@ -346,15 +370,6 @@ int wgrad_s2_try(const void* dy, int dy_cs, int dy_co, int Cout, const void* x, 
   p.tiles_per_row = (Wo + 63) / 64;
   p.n_tiles = N * Ho * p.tiles_per_row;
   const int jobs = p.co_tiles * 4;
-  // one block per CU (a block owns 120-150 KB of LDS): the grid must not exceed the CU count
-  const int n_cu = persistent_cus();
-  int S = n_cu / jobs;
-  if (S > p.n_tiles / 8) S = p.n_tiles / 8;
-  if (S > 256) S = 256;
-  if (S < 1) S = 1;
-  // per-tile scalar offsets are relative to the slab's first row: the slab's extent must fit 31 bits
-  const long long slab_rows = (long long)p.n_tiles / S / p.tiles_per_row + 4;
-  if ((2 * slab_rows + 8) * W * (long long)x_cs * 2 >= 0x7FF00000LL || slab_rows * Wo * (long long)dy_cs * 2 >= 0x7FF00000LL) return 0;
   const long long need = ((long long)S * 16 * Cout * CinTot + 256LL * Cout) * 4;
   if (workspace_bytes < need) {
     set_error("wgrad_s2: workspace too small (%lld < %lld)", workspace_bytes, need);

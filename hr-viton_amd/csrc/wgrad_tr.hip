@@ -355,15 +355,17 @@ __global__ __launch_bounds__(256) void conv_wgrad_tr_kernel(const WgradTrParams 
 
 // (bias gradient, second stage: the per-slab column sums are summed by the caller's wgrad_reduce_kernel launch)
 
-// Host side.  Returns 1 when the kernel was launched (partials in `workspace`, *S_out slabs), 0 when the shape is
-// not one it serves (the caller falls back to conv_wgrad_bf16_kernel), < 0 on error.
-int wgrad_tr_try(const void* dy, int dy_cs, int dy_co, int Cout, const void* x, int x_C, int x_cs, int x_co, int x_C_real,
-                 int ci_base, int CinTot, int N, int H, int W, int KH, int KW, int pad, float* workspace,
-                 long long workspace_bytes, float* dbias, int dbias_accumulate, hipStream_t st, int* S_out) {
+// The shape class (0..8) that serves this weight gradient, or -1: EVERY condition wgrad_tr_try applies before it launches, the
+// environment switches and the slab-extent limit included.  Fills the geometry fields of `p`, the cout tiles per wave `tm` and the
+// slab count `S`.  hrv_conv2d_wgrad_tr_supported answers from it as well, so a caller that has to prepare its operands differently
+// for the fallback kernel (train_ops.conv_wgrad: a bf16 dY padded to a multiple of 4 columns) asks the same code that decides.
+static int wgrad_tr_class(int dy_cs, int dy_co, int Cout, int x_C, int x_cs, int x_co, int N, int H, int W, int KH, int KW, int pad,
+                          WgradTrParams& p, int& tm, int& S) {
   const char* env = hrv::env("HRV_WGRAD_TR");
-  if (env && env[0] == '0') return 0;
-  if (KW < 1 || KW > 3 || KH != KW || pad != KH / 2) return 0;
-  if ((dy_cs | dy_co | x_cs | x_co | x_C) & 7) return 0;                         // 16-byte DMA granules (Cout itself may be
+  if (env && env[0] == '0') return -1;
+  if (KW < 1 || KW > 3 || KH != KW || pad != KH / 2) return -1;
+  if (Cout < 1 || x_C < 1 || N < 1 || H < 1 || W < 1) return -1;
+  if ((dy_cs | dy_co | x_cs | x_co | x_C) & 7) return -1;                        // 16-byte DMA granules (Cout itself may be
                                                                                   // anything: rows >= Cout are never written)
   const long long P = (long long)N * H * W;
   // low-resolution levels: weight-bound, old kernel.  HRV_WGRAD_TR_MIN_PIX: the smallest N*H*W this kernel takes -- 8192 since round 5
@@ -371,14 +373,12 @@ int wgrad_tr_try(const void* dy, int dy_cs, int dy_co, int Cout, const void* x, 
   // profiles/r05_ab_wgrad_tr_min.txt); 32768 before
   const char* emin = hrv::env("HRV_WGRAD_TR_MIN_PIX");
   const long long pmin = emin ? atoll(emin) : 8192;
-  if (P < (pmin > 0 ? pmin : 8192) || W < 32) return 0;
+  if (P < (pmin > 0 ? pmin : 8192) || W < 32) return -1;
   const int gpt = (x_C + 31) / 32;
   const int taps = KH * KW;
-  WgradTrParams p;
-  p.dy = dy; p.dy_cs = dy_cs; p.dy_co = dy_co; p.Cout = Cout;
-  p.x = x; p.x_cs = x_cs; p.x_co = x_co; p.x_C = x_C;
+  p.dy_cs = dy_cs; p.dy_co = dy_co; p.Cout = Cout;
+  p.x_cs = x_cs; p.x_co = x_co; p.x_C = x_C;
   p.N = N; p.H = H; p.W = W; p.KH = KH; p.KW = KW; p.pad = pad;
-  p.CinTot = CinTot; p.ci_base = ci_base; p.ci_real = x_C_real;
   p.gpt = gpt;
   p.tiles_per_row = (W + 63) / 64;
   p.n_tiles = N * H * p.tiles_per_row;
@@ -386,7 +386,8 @@ int wgrad_tr_try(const void* dy, int dy_cs, int dy_co, int Cout, const void* x, 
   //                 1..3 = thin layers (<= 32 couts, <= 96 source channels): a block = every tap x every channel
   //                 4..7 = other source widths (round 4): 4: 144 / 160 channels (5 groups), 6: 272 / 288 (9), 7: 256 (8) -- a block =
   //                        the KW taps of one kernel row x all groups x 64 couts (row mode); 5: 64 channels x 64 couts, every tap
-  int cls = -1, tm = 0;
+  int cls = -1;
+  tm = 0;
   p.row_mode = 0;
   if (gpt == 4 && KW == 3) {
     cls = 0;
@@ -410,18 +411,39 @@ int wgrad_tr_try(const void* dy, int dy_cs, int dy_co, int Cout, const void* x, 
     cls = gpt == 3 ? (taps == 1 ? 3 : 1) : (gpt == 1 && taps == 9 ? 2 : -1);
     p.co_tiles = 1; p.col_tiles = 1; tm = 1;
   }
-  if (cls < 0) return 0;
+  if (cls < 0 || tm < 1 || tm > 5) return -1;
   const int jobs = p.co_tiles * p.col_tiles;
   // one block per CU (a block owns 126-152 KB of LDS): the grid must NOT exceed the CU count, or the surplus blocks
   // run as a second round on an otherwise idle chip (first build: 258 blocks, kernel time 2x the wave lifetime)
   const int n_cu = persistent_cus();
-  int S = n_cu / jobs;
+  S = n_cu / jobs;
   if (S > p.n_tiles / 8) S = p.n_tiles / 8;
   if (S > 256) S = 256;
   if (S < 1) S = 1;
   // per-tile scalar offsets are relative to the slab's first row: the slab's extent must fit 31 bits
   const long long slab_rows = p.n_tiles / S / p.tiles_per_row + 4 + KH;
-  if (slab_rows * W * (long long)(dy_cs > x_cs ? dy_cs : x_cs) * 2 >= 0x7FF00000LL) return 0;
+  if (slab_rows * W * (long long)(dy_cs > x_cs ? dy_cs : x_cs) * 2 >= 0x7FF00000LL) return -1;
+  return cls;
+}
+
+int wgrad_tr_serves(int dy_cs, int dy_co, int Cout, int x_C, int x_cs, int x_co, int N, int H, int W, int KH, int KW, int pad) {
+  WgradTrParams p;
+  int tm = 0, S = 0;
+  return wgrad_tr_class(dy_cs, dy_co, Cout, x_C, x_cs, x_co, N, H, W, KH, KW, pad, p, tm, S) + 1;
+}
+
+// Host side.  Returns 1 when the kernel was launched (partials in `workspace`, *S_out slabs), 0 when the shape is
+// not one it serves (the caller falls back to conv_wgrad_bf16_kernel), < 0 on error.
+int wgrad_tr_try(const void* dy, int dy_cs, int dy_co, int Cout, const void* x, int x_C, int x_cs, int x_co, int x_C_real,
+                 int ci_base, int CinTot, int N, int H, int W, int KH, int KW, int pad, float* workspace,
+                 long long workspace_bytes, float* dbias, int dbias_accumulate, hipStream_t st, int* S_out) {
+  WgradTrParams p;
+  int tm = 0, S = 0;
+  const int cls = wgrad_tr_class(dy_cs, dy_co, Cout, x_C, x_cs, x_co, N, H, W, KH, KW, pad, p, tm, S);
+  if (cls < 0) return 0;
+  p.dy = dy; p.x = x;
+  p.CinTot = CinTot; p.ci_base = ci_base; p.ci_real = x_C_real;
+  const int jobs = p.co_tiles * p.col_tiles;
   const long long need = ((long long)S * KH * KW * Cout * CinTot + 256LL * Cout) * 4;
   if (workspace_bytes < need) {
     set_error("wgrad_tr: workspace too small (%lld < %lld)", workspace_bytes, need);

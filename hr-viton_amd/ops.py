@@ -212,21 +212,24 @@ def profile_begin():
     _Prof.records = []
 
 
-def profile_end(kernels: bool = False):
+def profile_end(kernels: bool = False, variants: bool = False):
     """Returns [(kind, name, flops, bytes, ms)] for every launch since profile_begin(); ``kernels``: 6-tuples with the
-    name of the device kernel family that served the launch (what a rocprofv3 kernel trace groups by) at the end."""
+    name of the device kernel family that served the launch (what a rocprofv3 kernel trace groups by) at the end;
+    ``variants`` (with ``kernels``): the family followed by what the dispatcher chose inside it where one family has several
+    (``conv_p2_kernel[mode 1]``, ``conv_wgrad_tr_kernel[class 8]``, ``conv_wgrad_kernel[bf16 stored]``) -- the dispatcher sweep
+    of tests/test_gpu_conv_dispatch.py keys on it; the plain family stays the grouping key of bench.py's roofline."""
     _Prof.enabled = False
     torch.cuda.synchronize()
-    out = [((k, n, fl, by, s.elapsed_time(e), kn) if kernels else (k, n, fl, by, s.elapsed_time(e)))
-           for (k, n, fl, by, kn, s, e) in _Prof.records]
+    out = [((k, n, fl, by, s.elapsed_time(e), f"{kn}[{var}]" if (variants and var) else kn) if kernels else
+            (k, n, fl, by, s.elapsed_time(e))) for (k, n, fl, by, kn, var, s, e) in _Prof.records]
     _Prof.records = []
     return out
 
 
 class _Timed:
-    def __init__(self, kind, name, flops, nbytes, kernel=None):
+    def __init__(self, kind, name, flops, nbytes, kernel=None, variant=""):
         # ``kernel``: the hrv:: kernel (family) behind the C entry point; the launch kind stands in where one kind = one kernel
-        self.args = (kind, name, flops, nbytes, kernel or kind)
+        self.args = (kind, name, flops, nbytes, kernel or kind, variant)
 
     def __enter__(self):
         if _Prof.enabled:

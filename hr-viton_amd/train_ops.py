@@ -607,7 +607,7 @@ def conv_forward_dev(w: torch.Tensor, srcs: Sequence[Tuple[Act, int]], stride: i
             out = ops.alloc(N, Ho, Wo, Cout, a0.t.device, bf16=p2_bf)
         pk = conv_p2_pack(0, w, None, cin, Cout, sigma, wscale, frozen)
         return conv_p2(a0, pk, Cout, out, bias=shift, act=act, slope=slope, residual=residual, name=name,
-                       flops=2.0 * N * Ho * Wo * Cout * cin * 9)
+                       flops=2.0 * N * Ho * Wo * Cout * cin * 9, variant="mode 0")
     cfg = _bf16_tile(Cout) if mb else _f32_tile(N * Ho * Wo, Cout)
     if mb:                 # bf16-stored source: the halo patch stays in LDS (ops.patch_tile)
         if KH == 1 and KW == 1 and a0.bf16 and len(srcs) == 1 and a0.Cp <= 128 and Cout % 64 == 0:
@@ -695,7 +695,7 @@ def conv_dgrad(dy: Act, w, H: int, W: int, stride: int, pad: int, wscale: float 
         pk = (conv_p2_pack(2, pair[0], pair[1], Cout, cin) if pair is not None else
               conv_p2_pack(1, w, None, Cout, cin, sigma, wscale, frozen))
         return conv_p2(dy, pk, cin, out, mask=act_mask if res_mode == 1 else None, mask_slope=slope, name=name, flops=fl,
-                       residual=add_after, res_after_mask=add_after is not None)
+                       residual=add_after, res_after_mask=add_after is not None, variant="mode 2" if pair is not None else "mode 1")
     if stride == 1:
         if mb and (Ho, Wo) == (H, W):   # a stride-1 data gradient is a 'same' 3x3 convolution over dY
             cfg = ops.patch_tile(dy.bf16, KH, KW, 1, KH - 1 - pad, 1, 0, dy.Cp, cin, N, H, W) or cfg
@@ -742,20 +742,29 @@ def conv_wgrad(dy: Act, x: Act, x_up: int, ci_base: int, cin_tot: int, KH: int, 
                                                     _stream()), f"hrv_conv_cout1_wgrad_f32[{name}]")
         return
     wo_real = Wo
-    tr2 = (stride == 1 and (Ho, Wo) == (H, W) and KH == KW == 2 and pad == 1 and x_up == 0 and Cout % 64 == 0 and 32 < x.Cp <= 64 and
-           N * Ho * Wo >= 8192 and os.environ.get("HRV_WGRAD_TR", "1") != "0")          # (wgrad_tr.hip's 2x2 class takes any width)
-    if (not tr2 and MMA_BF16[0] and dy.bf16 and x.bf16 and x_up == 0 and (KH, KW, stride, pad) == (4, 4, 2, 2) and
-            (Ho, Wo) == (H // 2 + 1, W // 2 + 1) and
-            lib.hrv_conv2d_wgrad_s2_supported(Cout, x.Cp, x.cstride, x.coff, dy.cstride, dy.coff, N, H, W)):
-        tr2 = True                      # (wgrad_s2.hip: any width as well)
-    if MMA_BF16[0] and Wo % 4 != 0 and dy.bf16 and x.bf16 and dy.coff == 0 and dy.cstride == dy.C and dy.C % 8 == 0 and not tr2:
+    # The LDS-DMA kernels for bf16-stored operands take any width; the quad-staged kernel behind them needs Wo % 4 == 0.  Which one
+    # will run is the C launch path's own decision (hrv_conv2d_wgrad_{tr,s2}_supported answer from the code that launches: switches,
+    # pixel, width and slab-extent limits included), asked here with the conditions wgrad_impl (csrc/conv_bwd.hip) puts in front of
+    # each try: edit both places together.
+    served = ""
+    if MMA_BF16[0] and dy.bf16 and x.bf16 and x_up == 0:
+        if stride == 1 and (Ho, Wo) == (H, W):
+            c = lib.hrv_conv2d_wgrad_tr_supported(Cout, x.Cp, x.cstride, x.coff, dy.cstride, dy.coff, N, H, W, KH, KW, pad)
+            if c > 0:
+                served = f"conv_wgrad_tr_kernel[class {c - 1}]"
+        elif (KH, KW, stride, pad) == (4, 4, 2, 2) and (Ho, Wo) == (H // 2 + 1, W // 2 + 1):
+            c = lib.hrv_conv2d_wgrad_s2_supported(Cout, x.Cp, x.cstride, x.coff, dy.cstride, dy.coff, N, H, W)
+            if c > 0:
+                served = "conv_wgrad_s2_kernel"
+    if MMA_BF16[0] and Wo % 4 != 0 and dy.bf16 and x.bf16 and dy.coff == 0 and dy.cstride == dy.C and dy.C % 8 == 0 and not served:
         dy = pad_width_bf16(dy)          # (the same zero columns for a bf16-stored dY: the PatchGAN with bf16 feature maps)
         Wo = dy.W
     if (MMA_BF16[0] and Wo % 4 != 0 and Wo >= 32 and not (x.bf16 or dy.bf16) and dy.coff == 0 and dy.cstride == dy.Cp):
         # odd-sized maps (the PatchGAN's 513 / 257 / 129 columns): the bf16 matrix-core kernel stages quads of 4 pixels
         # of one image row, so dY gets zero columns up to the next multiple of 4 -- they add nothing to dW or the bias
         # gradient (the X taps they would pair with are never weighted) -- instead of taking the fp32 kernel (60-100 TFLOP/s)
-        dy = Act(torch.nn.functional.pad(dy.t, (0, 0, 0, (-Wo) % 4)), dy.C)
+        with _Timed("layout", "pad_width", 0.0, 2.0 * ops.act_bytes(dy)):
+            dy = Act(torch.nn.functional.pad(dy.t, (0, 0, 0, (-Wo) % 4)), dy.C)
         Wo = dy.W
     need = lib.hrv_conv2d_wgrad_workspace_bytes(Cout, cin_tot, KH, KW, N * Ho * Wo)
     ws = _workspace(dy.t.device, need)
@@ -766,14 +775,24 @@ def conv_wgrad(dy: Act, x: Act, x_up: int, ci_base: int, cin_tot: int, KH: int, 
             cin_tot, N, H, W, Ho, Wo, KH, KW, stride, pad, ws.data_ptr(), ws.numel() * 4, dw.data_ptr(),
             1 if accumulate else 0, None if dbias is None else dbias.data_ptr(), 1 if dbias_accumulate else 0)
     nbytes = ops.act_bytes(dy) + ops.act_bytes(x) + 4.0 * Cout * x.C * KH * KW
-    with _Timed("wgrad", name, fl, nbytes, "conv_wgrad_tr_kernel" if (x.bf16 or dy.bf16) else "conv_wgrad_kernel"):
+    # the device kernel that serves the launch (what a rocprofv3 kernel trace groups by): the LDS-DMA kernels where C takes them, else
+    # the generic kernel by its arithmetic and storage types
+    if served:
+        kern, _, var = served.partition("[")
+        var = var.rstrip("]")
+    elif x.bf16 or dy.bf16:
+        kern, var = "conv_wgrad_kernel", "bf16 stored" if dy.bf16 else "bf16 x-stored"
+    else:
+        kern, var = "conv_wgrad_kernel", "bf16" if fn is lib.hrv_conv2d_wgrad_bf16mma_nhwc_f32 else "fp32"
+    with _Timed("wgrad", name, fl, nbytes, kern, var):
         if x.bf16 or dy.bf16:
-            assert MMA_BF16[0] and (Wo % 4 == 0 or tr2), f"{name}: bf16-stored operands need the bf16 matrix-core weight gradient"
+            assert MMA_BF16[0] and (Wo % 4 == 0 or served), f"{name}: bf16-stored operands need the bf16 matrix-core weight gradient"
             assert x.bf16, f"{name}: bf16 dY with an fp32 X is not built"
             _lib.check(lib.hrv_conv2d_wgrad_bf16mma_st_nhwc_f32(*args, (1 if dy.bf16 else 0) | 2, _stream()),
                        "hrv_conv2d_wgrad_bf16mma_st_nhwc_f32")
         else:
-            _lib.check(fn(*args, _stream()), "hrv_conv2d_wgrad_nhwc_f32")
+            _lib.check(fn(*args, _stream()), "hrv_conv2d_wgrad_bf16mma_nhwc_f32" if fn is lib.hrv_conv2d_wgrad_bf16mma_nhwc_f32
+                       else "hrv_conv2d_wgrad_nhwc_f32")
 
 
 def colsum(a: Act, out: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
@@ -1158,7 +1177,8 @@ def act_bwd_(d: Act, y: Act, act: int, slope: float = 0.2):
 def scale_(x: torch.Tensor, s_host: float = 1.0, s_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
     lib = _lib.load()
     fn = lib.hrv_scale_bf16 if x.dtype == torch.bfloat16 else lib.hrv_scale_f32      # (a bf16 loss gradient: PatchGAN feature taps)
-    _lib.check(fn(x.data_ptr(), x.numel(), s_host, None if s_dev is None else s_dev.data_ptr(), _stream()), "hrv_scale_f32")
+    _lib.check(fn(x.data_ptr(), x.numel(), s_host, None if s_dev is None else s_dev.data_ptr(), _stream()),
+               "hrv_scale_bf16" if x.dtype == torch.bfloat16 else "hrv_scale_f32")
     return x
 
 
@@ -1474,8 +1494,9 @@ def conv_p2_pack(mode: int, w: torch.Tensor, w2: Optional[torch.Tensor], K: int,
 
 def conv_p2(src: Act, packed: torch.Tensor, cols: int, out: Act, bias: Optional[torch.Tensor] = None, act: int = ACT_NONE, slope: float = 0.2,
             mask: Optional[Act] = None, mask_slope: float = 0.0, name: str = "conv", flops: float = 0.0, tag: str = "",
-            residual: Optional[Act] = None, res_after_mask: bool = False):
-    """out = act(conv3x3(src) + bias [+ residual]) [* (mask > 0 ? 1 : mask_slope)] [+ residual if res_after_mask] on csrc/conv_p2.hip."""
+            residual: Optional[Act] = None, res_after_mask: bool = False, variant: str = ""):
+    """out = act(conv3x3(src) + bias [+ residual]) [* (mask > 0 ? 1 : mask_slope)] [+ residual if res_after_mask] on csrc/conv_p2.hip.
+    ``variant``: what the caller packed (the weight stream's mode), for the launch record."""
     lib = _lib.load()
     assert src.bf16 and out.C == cols
     d = _lib.hrv_conv_p2_t()
@@ -1495,7 +1516,7 @@ def conv_p2(src: Act, packed: torch.Tensor, cols: int, out: Act, bias: Optional[
         d.res_after_mask = 1 if res_after_mask else 0
     nb = (ops.act_bytes(src) + ops.act_bytes(out) + (ops.act_bytes(mask) if mask is not None else 0.0) +
           (ops.act_bytes(residual) if residual is not None else 0.0) + 2.0 * src.C * cols * 9)
-    with ops._Timed("conv", name + tag, flops, nb, "conv_p2_kernel"):
+    with ops._Timed("conv", name + tag, flops, nb, "conv_p2_kernel", variant):
         _lib.check(lib.hrv_conv_p2_bf16(C.byref(d), _stream()), f"hrv_conv_p2_bf16[{name}]")
     return out
 

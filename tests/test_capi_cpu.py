@@ -215,3 +215,17 @@ def test_conv_s2_host_logic(lib):
     assert ws(128, 64, 64, 0, 128, 0, 8, 513, 385) == 1 and ws(256, 128, 128, 0, 256, 0, 8, 257, 193) == 1
     assert ws(128, 64, 192, 0, 128, 0, 8, 257, 193) == 1          # X as the hi third of a split tensor
     assert ws(96, 64, 64, 0, 96, 0, 8, 513, 385) == 0 and ws(128, 64, 64, 0, 128, 0, 1, 33, 33) == 0
+    # hrv_conv2d_wgrad_tr_supported(Cout, x_C, x_cstride, x_coff, dy_cstride, dy_coff, N, H, W, KH, KW, pad): 1 + the class
+    # wgrad_tr_try will take, 0 where it declines (train_ops.conv_wgrad pads a bf16 dY for the fallback kernel then)
+    wt = lib.hrv_conv2d_wgrad_tr_supported
+    assert wt(256, 128, 128, 0, 256, 0, 4, 128, 96, 3, 3, 1) == 1 and wt(64, 144, 144, 0, 64, 0, 4, 256, 192, 3, 3, 1) == 5
+    assert wt(64, 48, 48, 0, 64, 0, 4, 513, 385, 2, 2, 1) == 9                     # PatchGAN's model0 over its space-to-depth image
+    assert wt(64, 48, 48, 0, 64, 0, 1, 280, 30, 2, 2, 1) == 0                      # W < 32: 8400 pixels are not enough
+    assert wt(64, 48, 48, 0, 64, 0, 1, 256, 32, 2, 2, 1) == 9 and wt(64, 48, 48, 0, 64, 0, 1, 265, 31, 2, 2, 1) == 0     # W >= 32 exactly
+    assert wt(64, 48, 48, 0, 64, 0, 1, 293, 28, 2, 2, 1) == 0 and wt(64, 64, 64, 0, 64, 0, 1, 249, 33, 3, 3, 1) == 6
+    assert wt(64, 64, 200, 64, 64, 0, 1, 64, 128, 3, 3, 1) == 6 and wt(64, 64, 200, 68, 64, 0, 1, 64, 128, 3, 3, 1) == 0  # x slice granule
+    assert wt(64, 64, 204, 64, 64, 0, 1, 64, 128, 3, 3, 1) == 0 and wt(64, 64, 64, 0, 80, 4, 1, 64, 128, 3, 3, 1) == 0   # cstride, dY slice
+    assert ws(128, 64, 200, 64, 128, 0, 1, 254, 126) == 1 and ws(128, 64, 200, 68, 128, 0, 1, 254, 126) == 0
+    assert wt(64, 48, 48, 0, 64, 0, 1, 64, 127, 2, 2, 1) == 0 and wt(64, 48, 48, 0, 64, 0, 1, 64, 128, 2, 2, 1) == 9      # N*H*W >= 8192
+    assert wt(60, 64, 64, 0, 64, 0, 1, 64, 128, 3, 3, 1) == 0 and wt(64, 64, 64, 4, 64, 0, 1, 64, 128, 3, 3, 1) == 0     # Cout % 64, granule
+    assert wt(64, 64, 64, 0, 64, 0, 1, 64, 128, 3, 3, 0) == 0 and wt(64, 64, 64, 0, 64, 0, 1, 64, 128, 4, 4, 2) == 0     # 'same' 1x1..3x3 only
