@@ -170,6 +170,8 @@ SYMBOLS = {
     "hrv_persistent_cus": (C.c_int, []),
     "hrv_diag_set_tlog": (C.c_int, [_vp, _i64]),
     "hrv_diag_reload_env": (C.c_int, []),
+    "hrv_diag_norm_bwd_instances": (C.c_char_p, []),
+    "hrv_diag_norm_bwd_route": (C.c_int, [C.POINTER(hrv_norm_bwd_t), C.POINTER(hrv_norm_bwd_t)]),
     "hrv_conv2d_pick_tile": (C.c_int, [_i64, _i32]),
     "hrv_conv2d_tile_bn": (C.c_int, [_i32]),
     "hrv_conv2d_tile_bm": (C.c_int, [_i32]),
@@ -197,6 +199,7 @@ SYMBOLS = {
     "hrv_colsum_nhwc_f32": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _i32, _vp]),
     "hrv_norm_bwd_workspace_elems": (_i64, [_i32, _i32, _i32, _i32]),
     "hrv_spade_norm_bwd2_nhwc_f32": (C.c_int, [C.POINTER(hrv_norm_bwd_t), C.POINTER(hrv_norm_bwd_t), _vp]),
+    "hrv_spade_norm_bwd2_supported": (C.c_int, [C.POINTER(hrv_norm_bwd_t), C.POINTER(hrv_norm_bwd_t)]),
     "hrv_spade_norm_bwd_nhwc_f32": (C.c_int, [C.POINTER(hrv_norm_bwd_t), _vp]),
     "hrv_thin_conv_supported": (C.c_int, [_i32, _i32, _i32, _i32]),
     "hrv_thin_conv_bf16": (C.c_int, [C.POINTER(hrv_thin_conv_t), _vp]),

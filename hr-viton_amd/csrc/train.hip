@@ -5,6 +5,8 @@
 // fixed summation order (deterministic).
 #include <string.h>
 
+#include <string>
+
 #include "hrv_common.h"
 
 namespace hrv {
@@ -45,11 +47,14 @@ struct XThread {
   const float* base;      // channel group g of pixel 0 of sample n
   int cs, lo, W, Wl;
 };
+// UP: whether x is the up-sampled pair, known when the kernel is compiled (0 / 1) or read from the source (-1)
+template <int UP = -1>
 __device__ __forceinline__ XThread xsrc_thread(const XSrc& s, int n, int g) {
   XThread t;
+  const bool up = UP < 0 ? s.up_g > 0 : UP != 0;
   t.W = s.W; t.Wl = s.W >> 1;
-  t.lo = (s.up_g > 0 && g < s.up_g) ? 1 : 0;
-  if (s.up_g > 0 && !t.lo) {
+  t.lo = (up && g < s.up_g) ? 1 : 0;
+  if (up && !t.lo) {
     t.cs = s.x2_cs;
     t.base = s.x2 + (size_t)n * s.H * s.W * s.x2_cs + s.x2_co + (g - s.up_g) * 4;
   } else {
@@ -85,6 +90,10 @@ struct NormBwdParams {
   int dbeta_in_place;                        // dout IS the dbeta half of dgb (its producer wrote it there, activation derivative applied): not stored again
 };
 
+// Stage 1 pins its roundings (fp contract(off) + the two fused multiply-adds written out): left to the compiler, which products
+// fuse into a following add depends on the surrounding code, and an instance must round exactly as the generic kernel does --
+// v = fma(z, noise_scale, x) and s2 = fma(dnh, nh, s2) are the two it has always fused; dnh and dgamma are rounded products.
+__device__ __forceinline__ f32x4 fma4(f32x4 a, f32x4 b, f32x4 c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ f32x4 ld4_bf16(const void* base, size_t elem) {
   const uint2 u = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(base) + elem);
@@ -98,7 +107,27 @@ __device__ __forceinline__ void st4_bf16(void* base, size_t elem, f32x4 v) {
   *reinterpret_cast<bf16x4t*>(reinterpret_cast<unsigned short*>(base) + elem) = __builtin_convertvector(v, bf16x4t);
 }
 
-__global__ __launch_bounds__(256) void norm_bwd_stage1_kernel(const NormBwdParams p) {
+
+// ---- the storage form of a normalisation backward as one word.  The generic kernels (F < 0) read every choice from the parameter
+// block at run time, as they always did; an instance (F >= 0) is compiled for one form, so its two-pixel body has no branch and
+// keeps one storage form of each operand in registers.  Same statements, same order: an instance is bit-identical to the generic
+// kernel on a descriptor of its form (norm_form_of() below is the only place that derives the word).
+enum : int {
+  NF_DOUT_BF16 = 1 << 0, NF_ACT_SHIFT = 1, NF_ACT_MASK = 3 << NF_ACT_SHIFT /* HRV_ACT_NONE / RELU / LRELU */, NF_OUT_BF16 = 1 << 3,
+  NF_G1P = 1 << 4, NF_G1P_BF16 = 1 << 5, NF_DNH_BF16 = 1 << 6, NF_DGB = 1 << 7, NF_DGB_BF16 = 1 << 8, NF_DBETA_IN_PLACE = 1 << 9,
+  NF_NOISE = 1 << 10, NF_UP = 1 << 11, NF_DX_BF16 = 1 << 12, NF_DX_ACC = 1 << 13,
+  NF_STAGE2 = NF_DNH_BF16 | NF_NOISE | NF_UP | NF_DX_BF16 | NF_DX_ACC,       // what stage 2 depends on
+  NF_STAGE1 = (NF_DX_BF16 - 1)                                               // ... and stage 1: everything but the dx bits
+};
+template <int F> struct NormForm {
+  static __device__ __forceinline__ bool is(int bit, int run_time) { return F < 0 ? run_time != 0 : (F & bit) != 0; }
+  static __device__ __forceinline__ int act(int run_time) { return F < 0 ? run_time : (F & NF_ACT_MASK) >> NF_ACT_SHIFT; }
+  static constexpr int up = F < 0 ? -1 : ((F & NF_UP) ? 1 : 0);
+};
+
+template <int F>
+__device__ __forceinline__ void norm_bwd_stage1_body(const NormBwdParams& p) {
+  typedef NormForm<F> Fm;
   __shared__ f32x4 red[2][256];
   const int n = blockIdx.y, b = blockIdx.x, t = threadIdx.x;
   const int HW = p.H * p.W, C = p.C4 * 4;
@@ -112,8 +141,10 @@ __global__ __launch_bounds__(256) void norm_bwd_stage1_kernel(const NormBwdParam
     f32x4 s1 = (f32x4)(0.f), s2 = (f32x4)(0.f);
     if (r < R && g < p.C4) {
       const f32x4 mu = ld4(p.mean + (size_t)n * C + g * 4), rs = ld4(p.rstd + (size_t)n * C + g * 4);
-      const f32x4 ns4 = p.z ? ld4(p.ns + g * 4) : (f32x4)(0.f);
-      const XThread xt = xsrc_thread(p.xs, n, g);
+      const bool noise = Fm::is(NF_NOISE, p.z != nullptr), has_g1p = Fm::is(NF_G1P, p.g1p != nullptr), has_dgb = Fm::is(NF_DGB, p.dgb != nullptr);
+      const int act = Fm::act(p.act);
+      const f32x4 ns4 = noise ? ld4(p.ns + g * 4) : (f32x4)(0.f);
+      const XThread xt = xsrc_thread<Fm::up>(p.xs, n, g);
       // two pixels per iteration: all eight loads of both are requested before the first result is stored (the stores may
       // alias the loads as far as the compiler knows, so a plain loop keeps one pixel's four loads in flight per thread);
       // every value and the order of the two sums are those of the plain loop
@@ -123,49 +154,51 @@ __global__ __launch_bounds__(256) void norm_bwd_stage1_kernel(const NormBwdParam
         const size_t pix = (size_t)n * HW + px;
         L.v = ld4(xsrc_ptr(xt, px));
         L.zz = 0.f;
-        if (p.z) {
+        if (noise) {
           const int h = px / p.W, w = px - h * p.W;
           L.zz = p.z[((size_t)n * p.W + w) * p.H + h];
         }
-        L.d = p.dout_bf16 ? ld4_bf16(p.dout, pix * p.do_cs + p.do_co + g * 4) : ld4(p.dout + pix * p.do_cs + p.do_co + g * 4);
+        L.d = Fm::is(NF_DOUT_BF16, p.dout_bf16) ? ld4_bf16(p.dout, pix * p.do_cs + p.do_co + g * 4) : ld4(p.dout + pix * p.do_cs + p.do_co + g * 4);
         L.o = (f32x4)(0.f);
-        if (p.act != HRV_ACT_NONE) {
+        if (act != HRV_ACT_NONE) {
           const size_t oe = pix * p.out_cs + p.out_co + g * 4;
-          L.o = p.out_bf16 ? ld4_bf16(p.out, oe) : ld4(p.out + oe);
+          L.o = Fm::is(NF_OUT_BF16, p.out_bf16) ? ld4_bf16(p.out, oe) : ld4(p.out + oe);
         }
         L.g1 = (f32x4)(1.f);
-        if (p.g1p) {
+        if (has_g1p) {
           const size_t ge1 = pix * p.g_cs + p.g_co + g * 4;
-          L.g1 = p.g1p_bf16 ? ld4_bf16(p.g1p, ge1) : ld4(p.g1p + ge1);
+          L.g1 = Fm::is(NF_G1P_BF16, p.g1p_bf16) ? ld4_bf16(p.g1p, ge1) : ld4(p.g1p + ge1);
         }
         return L;
       };
       auto finish = [&](int px, const In& L) {
+#pragma clang fp contract(off)      // (see fma4)
         const size_t pix = (size_t)n * HW + px;
         f32x4 v = L.v;
-        if (p.z) v += L.zz * ns4;
+        if (noise) v = fma4((f32x4)(L.zz), ns4, v);
         const f32x4 nh = (v - mu) * rs;
         f32x4 dpre = L.d;
-        if (p.act != HRV_ACT_NONE) {
+        if (act != HRV_ACT_NONE) {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) dpre[e] *= dact(L.o[e], p.act, p.slope);
+          for (int e = 0; e < 4; ++e) dpre[e] *= dact(L.o[e], act, p.slope);
         }
         f32x4 dnh = dpre;
-        if (p.g1p) dnh *= L.g1;
-        if (p.dnh_bf16) st4_bf16(p.dnh, pix * p.dn_cs + p.dn_co + g * 4, dnh);
+        if (has_g1p) dnh *= L.g1;
+        if (Fm::is(NF_DNH_BF16, p.dnh_bf16)) st4_bf16(p.dnh, pix * p.dn_cs + p.dn_co + g * 4, dnh);
         else *reinterpret_cast<f32x4*>(p.dnh + pix * p.dn_cs + p.dn_co + g * 4) = dnh;
-        if (p.dgb) {
+        if (has_dgb) {
+          const bool keep_dbeta = Fm::is(NF_DBETA_IN_PLACE, p.dbeta_in_place);
           const size_t ge = pix * p.dgb_cs + p.dgb_co + g * 4;
-          if (p.dgb_bf16) {
+          if (Fm::is(NF_DGB_BF16, p.dgb_bf16)) {
             st4_bf16(p.dgb, ge, dpre * nh);
-            if (!p.dbeta_in_place) st4_bf16(p.dgb, ge + C, dpre);
+            if (!keep_dbeta) st4_bf16(p.dgb, ge + C, dpre);
           } else {
             *reinterpret_cast<f32x4*>(p.dgb + ge) = dpre * nh;
-            if (!p.dbeta_in_place) *reinterpret_cast<f32x4*>(p.dgb + ge + C) = dpre;
+            if (!keep_dbeta) *reinterpret_cast<f32x4*>(p.dgb + ge + C) = dpre;
           }
         }
         s1 += dnh;
-        s2 += dnh * nh;
+        s2 = fma4(dnh, nh, s2);
       };
       int px = p0 + r;
       for (; px + R < p1; px += 2 * R) {
@@ -186,6 +219,9 @@ __global__ __launch_bounds__(256) void norm_bwd_stage1_kernel(const NormBwdParam
     }
   }
 }
+__global__ __launch_bounds__(256) void norm_bwd_stage1_kernel(const NormBwdParams p) { norm_bwd_stage1_body<-1>(p); }
+template <int F>
+__global__ __launch_bounds__(256) void norm_bwd_stage1_inst(const NormBwdParams p) { norm_bwd_stage1_body<F>(p); }
 
 // fixed-order reduction of the slab partials: m1[n][c] = S1/HW, m2[n][c] = S2/HW
 // 16 lanes per (sample, channel): lane l sums slabs l, l + 16, ... in double, then a fixed butterfly inside the 16-lane group
@@ -227,7 +263,9 @@ struct NormBwd2Params {
   int NB; float* part;  // [N][NB][C] (only when z != NULL)
 };
 
-__global__ __launch_bounds__(256) void norm_bwd_stage2_kernel(const NormBwd2Params p) {
+template <int F>
+__device__ __forceinline__ void norm_bwd_stage2_body(const NormBwd2Params& p) {
+  typedef NormForm<F> Fm;
   __shared__ f32x4 red[256];
   const int n = blockIdx.y, b = blockIdx.x, t = threadIdx.x;
   const int HW = p.H * p.W, C = p.C4 * 4;
@@ -242,8 +280,9 @@ __global__ __launch_bounds__(256) void norm_bwd_stage2_kernel(const NormBwd2Para
     if (r < R && g < p.C4) {
       const size_t sc = (size_t)n * C + g * 4;
       const f32x4 mu = ld4(p.mean + sc), rs = ld4(p.rstd + sc), a1 = ld4(p.m1 + sc), a2 = ld4(p.m2 + sc);
-      const f32x4 ns4 = p.z ? ld4(p.ns + g * 4) : (f32x4)(0.f);
-      const XThread xt = xsrc_thread(p.xs, n, g);
+      const bool noise = Fm::is(NF_NOISE, p.z != nullptr), dx_bf16 = Fm::is(NF_DX_BF16, p.dx_bf16), acc = Fm::is(NF_DX_ACC, p.accumulate);
+      const f32x4 ns4 = noise ? ld4(p.ns + g * 4) : (f32x4)(0.f);
+      const XThread xt = xsrc_thread<Fm::up>(p.xs, n, g);
       // two pixels per iteration, loads of both first (see stage 1); values and the order of the sum are unchanged
       struct In { f32x4 v, dn, acc; float zz; };
       auto load = [&](int px) {
@@ -251,29 +290,29 @@ __global__ __launch_bounds__(256) void norm_bwd_stage2_kernel(const NormBwd2Para
         const size_t pix = (size_t)n * HW + px;
         L.v = ld4(xsrc_ptr(xt, px));
         L.zz = 0.f;
-        if (p.z) {
+        if (noise) {
           const int h = px / p.W, w = px - h * p.W;
           L.zz = p.z[((size_t)n * p.W + w) * p.H + h];
         }
         const size_t de = pix * p.dn_cs + p.dn_co + g * 4;
-        L.dn = p.dnh_bf16 ? ld4_bf16(p.dnh, de) : ld4(p.dnh + de);
+        L.dn = Fm::is(NF_DNH_BF16, p.dnh_bf16) ? ld4_bf16(p.dnh, de) : ld4(p.dnh + de);
         L.acc = (f32x4)(0.f);
-        if (!p.dx_bf16 && p.accumulate) L.acc = ld4(p.dx + pix * p.dx_cs + p.dx_co + g * 4);
+        if (!dx_bf16 && acc) L.acc = ld4(p.dx + pix * p.dx_cs + p.dx_co + g * 4);
         return L;
       };
       auto finish = [&](int px, const In& L) {
 #pragma clang fp contract(off)      // (norm_bwd2_stage2_kernel computes the same values in one pass: keep the roundings identical)
         const size_t pix = (size_t)n * HW + px;
         f32x4 v = L.v;
-        if (p.z) v += L.zz * ns4;
+        if (noise) v += L.zz * ns4;
         const f32x4 nh = (v - mu) * rs;
         f32x4 d = rs * (L.dn - a1 - nh * a2);
         sz += d * L.zz;
-        if (p.dx_bf16) {
+        if (dx_bf16) {
           st4_bf16(p.dx, pix * p.dx_cs + p.dx_co + g * 4, d);
         } else {
           float* o = p.dx + pix * p.dx_cs + p.dx_co + g * 4;
-          if (p.accumulate) d += L.acc;
+          if (acc) d += L.acc;
           *reinterpret_cast<f32x4*>(o) = d;
         }
       };
@@ -285,7 +324,7 @@ __global__ __launch_bounds__(256) void norm_bwd_stage2_kernel(const NormBwd2Para
       }
       if (px < p1) finish(px, load(px));
     }
-    if (p.z) {
+    if (Fm::is(NF_NOISE, p.z != nullptr)) {
       red[t] = sz;
       __syncthreads();
       if (r == 0 && g < p.C4) {
@@ -295,12 +334,18 @@ __global__ __launch_bounds__(256) void norm_bwd_stage2_kernel(const NormBwd2Para
     }
   }
 }
+__global__ __launch_bounds__(256) void norm_bwd_stage2_kernel(const NormBwd2Params p) { norm_bwd_stage2_body<-1>(p); }
+template <int F>
+__global__ __launch_bounds__(256) void norm_bwd_stage2_inst(const NormBwd2Params p) { norm_bwd_stage2_body<F>(p); }
 
 // ---- two normalisations over the SAME x (norm_0 and norm_s of a learned-shortcut SPADEResBlock both normalise the block
 // input, network_generator.py:158-166): x is read once per stage, dx = dx_a + dx_b is written once (no read-modify-write of
 // the first norm's result).  Every value is computed as in the single kernels (dx: one fp32 add, commutative), so the results
 // are bit-identical to two sequential calls with dx_accumulate on the second.
-__global__ __launch_bounds__(256) void norm_bwd2_stage1_kernel(const NormBwdParams pa, const NormBwdParams pb) {
+// (an instance serves two norms of the SAME form F)
+template <int F>
+__device__ __forceinline__ void norm_bwd2_stage1_body(const NormBwdParams& pa, const NormBwdParams& pb) {
+  typedef NormForm<F> Fm;
   __shared__ f32x4 red[4][256];
   const NormBwdParams& p = pa;                       // geometry and x are shared
   const int n = blockIdx.y, b = blockIdx.x, t = threadIdx.x;
@@ -315,25 +360,25 @@ __global__ __launch_bounds__(256) void norm_bwd2_stage1_kernel(const NormBwdPara
   if (r < R && g < p.C4) {
     const f32x4 mua = ld4(pa.mean + (size_t)n * C + g * 4), rsa = ld4(pa.rstd + (size_t)n * C + g * 4);
     const f32x4 mub = ld4(pb.mean + (size_t)n * C + g * 4), rsb = ld4(pb.rstd + (size_t)n * C + g * 4);
-    const f32x4 nsa = pa.z ? ld4(pa.ns + g * 4) : (f32x4)(0.f), nsb = pb.z ? ld4(pb.ns + g * 4) : (f32x4)(0.f);
-    const XThread xt = xsrc_thread(p.xs, n, g);
+    const f32x4 nsa = Fm::is(NF_NOISE, pa.z != nullptr) ? ld4(pa.ns + g * 4) : (f32x4)(0.f), nsb = Fm::is(NF_NOISE, pb.z != nullptr) ? ld4(pb.ns + g * 4) : (f32x4)(0.f);
+    const XThread xt = xsrc_thread<Fm::up>(p.xs, n, g);
     struct In1 { f32x4 d, o, g1; float zz; };
     struct In { f32x4 v; In1 a, b; };
     // (the per-norm pieces take their parameter block by reference to the kernel argument itself: no pointer tables, which
     //  would force the arguments into scratch memory)
     auto load1 = [&](const NormBwdParams& q, size_t pix, int h, int w) {
       In1 L;
-      L.zz = q.z ? q.z[((size_t)n * p.W + w) * p.H + h] : 0.f;
-      L.d = q.dout_bf16 ? ld4_bf16(q.dout, pix * q.do_cs + q.do_co + g * 4) : ld4(q.dout + pix * q.do_cs + q.do_co + g * 4);
+      L.zz = Fm::is(NF_NOISE, q.z != nullptr) ? q.z[((size_t)n * p.W + w) * p.H + h] : 0.f;
+      L.d = Fm::is(NF_DOUT_BF16, q.dout_bf16) ? ld4_bf16(q.dout, pix * q.do_cs + q.do_co + g * 4) : ld4(q.dout + pix * q.do_cs + q.do_co + g * 4);
       L.o = (f32x4)(0.f);
-      if (q.act != HRV_ACT_NONE) {
+      if (Fm::act(q.act) != HRV_ACT_NONE) {
         const size_t oe = pix * q.out_cs + q.out_co + g * 4;
-        L.o = q.out_bf16 ? ld4_bf16(q.out, oe) : ld4(q.out + oe);
+        L.o = Fm::is(NF_OUT_BF16, q.out_bf16) ? ld4_bf16(q.out, oe) : ld4(q.out + oe);
       }
       L.g1 = (f32x4)(1.f);
-      if (q.g1p) {
+      if (Fm::is(NF_G1P, q.g1p != nullptr)) {
         const size_t ge1 = pix * q.g_cs + q.g_co + g * 4;
-        L.g1 = q.g1p_bf16 ? ld4_bf16(q.g1p, ge1) : ld4(q.g1p + ge1);
+        L.g1 = Fm::is(NF_G1P_BF16, q.g1p_bf16) ? ld4_bf16(q.g1p, ge1) : ld4(q.g1p + ge1);
       }
       return L;
     };
@@ -347,29 +392,31 @@ __global__ __launch_bounds__(256) void norm_bwd2_stage1_kernel(const NormBwdPara
       return L;
     };
     auto finish1 = [&](const NormBwdParams& q, size_t pix, f32x4 v, const In1& L, f32x4 mu, f32x4 rs, f32x4 ns4, f32x4& s1, f32x4& s2) {
-      if (q.z) v += L.zz * ns4;
+#pragma clang fp contract(off)      // (see fma4)
+      if (Fm::is(NF_NOISE, q.z != nullptr)) v = fma4((f32x4)(L.zz), ns4, v);
       const f32x4 nh = (v - mu) * rs;
       f32x4 dpre = L.d;
-      if (q.act != HRV_ACT_NONE) {
+      if (Fm::act(q.act) != HRV_ACT_NONE) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) dpre[e] *= dact(L.o[e], q.act, q.slope);
+        for (int e = 0; e < 4; ++e) dpre[e] *= dact(L.o[e], Fm::act(q.act), q.slope);
       }
       f32x4 dnh = dpre;
-      if (q.g1p) dnh *= L.g1;
-      if (q.dnh_bf16) st4_bf16(q.dnh, pix * q.dn_cs + q.dn_co + g * 4, dnh);
+      if (Fm::is(NF_G1P, q.g1p != nullptr)) dnh *= L.g1;
+      if (Fm::is(NF_DNH_BF16, q.dnh_bf16)) st4_bf16(q.dnh, pix * q.dn_cs + q.dn_co + g * 4, dnh);
       else *reinterpret_cast<f32x4*>(q.dnh + pix * q.dn_cs + q.dn_co + g * 4) = dnh;
-      if (q.dgb) {
+      if (Fm::is(NF_DGB, q.dgb != nullptr)) {
+        const bool keep_dbeta = Fm::is(NF_DBETA_IN_PLACE, q.dbeta_in_place);
         const size_t ge = pix * q.dgb_cs + q.dgb_co + g * 4;
-        if (q.dgb_bf16) {
+        if (Fm::is(NF_DGB_BF16, q.dgb_bf16)) {
           st4_bf16(q.dgb, ge, dpre * nh);
-          if (!q.dbeta_in_place) st4_bf16(q.dgb, ge + C, dpre);
+          if (!keep_dbeta) st4_bf16(q.dgb, ge + C, dpre);
         } else {
           *reinterpret_cast<f32x4*>(q.dgb + ge) = dpre * nh;
-          if (!q.dbeta_in_place) *reinterpret_cast<f32x4*>(q.dgb + ge + C) = dpre;
+          if (!keep_dbeta) *reinterpret_cast<f32x4*>(q.dgb + ge + C) = dpre;
         }
       }
       s1 += dnh;
-      s2 += dnh * nh;
+      s2 = fma4(dnh, nh, s2);
     };
     auto finish = [&](int px, const In& L) {
       const size_t pix = (size_t)n * HW + px;
@@ -377,7 +424,8 @@ __global__ __launch_bounds__(256) void norm_bwd2_stage1_kernel(const NormBwdPara
       finish1(pb, pix, L.v, L.b, mub, rsb, nsb, s1b, s2b);
     };
     // one pixel per iteration: its seven 16-byte loads (x + three per norm) are as many as the single kernel keeps in flight
-    // with two pixels, at half the registers of a two-pixel body (231 -> two waves per SIMD)
+    // with two pixels, at half the registers of a two-pixel body (generic: 231 -> two waves per SIMD; the instances: 133 / 163
+    // with two pixels, three waves, and scratch memory when capped at 128 -- 98 / 96 with one)
     for (int px = p0 + r; px < p1; px += R) finish(px, load(px));
   }
   red[0][t] = s1a; red[1][t] = s2a; red[2][t] = s1b; red[3][t] = s2b;
@@ -395,8 +443,13 @@ __global__ __launch_bounds__(256) void norm_bwd2_stage1_kernel(const NormBwdPara
     }
   }
 }
+__global__ __launch_bounds__(256) void norm_bwd2_stage1_kernel(const NormBwdParams pa, const NormBwdParams pb) { norm_bwd2_stage1_body<-1>(pa, pb); }
+template <int F>
+__global__ __launch_bounds__(256) void norm_bwd2_stage1_inst(const NormBwdParams pa, const NormBwdParams pb) { norm_bwd2_stage1_body<F>(pa, pb); }
 
-__global__ __launch_bounds__(256) void norm_bwd2_stage2_kernel(const NormBwd2Params pa, const NormBwd2Params pb) {
+template <int F>
+__device__ __forceinline__ void norm_bwd2_stage2_body(const NormBwd2Params& pa, const NormBwd2Params& pb) {
+  typedef NormForm<F> Fm;
   __shared__ f32x4 red[2][256];
   const NormBwd2Params& p = pa;
   const int n = blockIdx.y, b = blockIdx.x, t = threadIdx.x;
@@ -412,8 +465,9 @@ __global__ __launch_bounds__(256) void norm_bwd2_stage2_kernel(const NormBwd2Par
     const size_t sc = (size_t)n * C + g * 4;
     const f32x4 mua = ld4(pa.mean + sc), rsa = ld4(pa.rstd + sc), a1a = ld4(pa.m1 + sc), a2a = ld4(pa.m2 + sc);
     const f32x4 mub = ld4(pb.mean + sc), rsb = ld4(pb.rstd + sc), a1b = ld4(pb.m1 + sc), a2b = ld4(pb.m2 + sc);
-    const f32x4 nsa = pa.z ? ld4(pa.ns + g * 4) : (f32x4)(0.f), nsb = pb.z ? ld4(pb.ns + g * 4) : (f32x4)(0.f);
-    const XThread xt = xsrc_thread(p.xs, n, g);
+    const bool za = Fm::is(NF_NOISE, pa.z != nullptr), zb = Fm::is(NF_NOISE, pb.z != nullptr);
+    const f32x4 nsa = za ? ld4(pa.ns + g * 4) : (f32x4)(0.f), nsb = zb ? ld4(pb.ns + g * 4) : (f32x4)(0.f);
+    const XThread xt = xsrc_thread<Fm::up>(p.xs, n, g);
     struct In { f32x4 v, dna, dnb; float za, zb; };
     auto load = [&](int px) {
       In L;
@@ -421,19 +475,19 @@ __global__ __launch_bounds__(256) void norm_bwd2_stage2_kernel(const NormBwd2Par
       L.v = ld4(xsrc_ptr(xt, px));
       const int h = px / p.W, w = px - h * p.W;
       const size_t zi = ((size_t)n * p.W + w) * p.H + h;
-      L.za = pa.z ? pa.z[zi] : 0.f;
-      L.zb = pb.z ? pb.z[zi] : 0.f;
+      L.za = za ? pa.z[zi] : 0.f;
+      L.zb = zb ? pb.z[zi] : 0.f;
       const size_t dea = pix * pa.dn_cs + pa.dn_co + g * 4, deb = pix * pb.dn_cs + pb.dn_co + g * 4;
-      L.dna = pa.dnh_bf16 ? ld4_bf16(pa.dnh, dea) : ld4(pa.dnh + dea);
-      L.dnb = pb.dnh_bf16 ? ld4_bf16(pb.dnh, deb) : ld4(pb.dnh + deb);
+      L.dna = Fm::is(NF_DNH_BF16, pa.dnh_bf16) ? ld4_bf16(pa.dnh, dea) : ld4(pa.dnh + dea);
+      L.dnb = Fm::is(NF_DNH_BF16, pb.dnh_bf16) ? ld4_bf16(pb.dnh, deb) : ld4(pb.dnh + deb);
       return L;
     };
     auto finish = [&](int px, const In& L) {
 #pragma clang fp contract(off)      // (d_a and d_b are rounded products, their sum one add: as the two sequential calls compute them)
       const size_t pix = (size_t)n * HW + px;
       f32x4 va = L.v, vb = L.v;
-      if (pa.z) va += L.za * nsa;
-      if (pb.z) vb += L.zb * nsb;
+      if (za) va += L.za * nsa;
+      if (zb) vb += L.zb * nsb;
       const f32x4 nha = (va - mua) * rsa, nhb = (vb - mub) * rsb;
       const f32x4 da = rsa * (L.dna - a1a - nha * a2a);
       const f32x4 db = rsb * (L.dnb - a1b - nhb * a2b);
@@ -453,10 +507,13 @@ __global__ __launch_bounds__(256) void norm_bwd2_stage2_kernel(const NormBwd2Par
   __syncthreads();
   if (r == 0 && g < p.C4) {
     for (int rr = 1; rr < R; ++rr) { sza += red[0][rr * GB + gl]; szb += red[1][rr * GB + gl]; }
-    if (pa.z) *reinterpret_cast<f32x4*>(pa.part + ((size_t)n * p.NB + b) * C + g * 4) = sza;
-    if (pb.z) *reinterpret_cast<f32x4*>(pb.part + ((size_t)n * p.NB + b) * C + g * 4) = szb;
+    if (Fm::is(NF_NOISE, pa.z != nullptr)) *reinterpret_cast<f32x4*>(pa.part + ((size_t)n * p.NB + b) * C + g * 4) = sza;
+    if (Fm::is(NF_NOISE, pb.z != nullptr)) *reinterpret_cast<f32x4*>(pb.part + ((size_t)n * p.NB + b) * C + g * 4) = szb;
   }
 }
+__global__ __launch_bounds__(256) void norm_bwd2_stage2_kernel(const NormBwd2Params pa, const NormBwd2Params pb) { norm_bwd2_stage2_body<-1>(pa, pb); }
+template <int F>
+__global__ __launch_bounds__(256) void norm_bwd2_stage2_inst(const NormBwd2Params pa, const NormBwd2Params pb) { norm_bwd2_stage2_body<F>(pa, pb); }
 
 // ---------------------------------------------------------------------------
 // losses: value + gradient in one pass.  mode: 0 L1 |a-b| ; 1 hinge-D fake max(1+a,0) ;
@@ -1203,6 +1260,133 @@ static void norm_bwd_fill(const hrv_norm_bwd_t* d, NormBwdParams& p, NormBwd2Par
   q.N = d->N; q.H = d->H; q.W = d->W; q.C4 = C / 4; q.NB = nb; q.part = part;  // partials are free again in stage 2
 }
 
+// ---- compile-time instances.  The form word of a descriptor, and per kernel the table of forms that have an
+// instance; a form outside its table, or HRV_NORM_BWD_GENERIC=1, runs on the generic kernel exactly as before the instances existed.
+static int norm_form_of(const hrv_norm_bwd_t* d, const NormBwdParams& p) {
+  int f = 0;
+  if (d->dout_bf16) f |= NF_DOUT_BF16;
+  f |= (d->act << NF_ACT_SHIFT) & NF_ACT_MASK;          // (no table entry holds HRV_ACT_TANH: such a descriptor stays generic)
+  if (d->act != HRV_ACT_NONE && d->out_bf16) f |= NF_OUT_BF16;
+  if (d->g1p) f |= NF_G1P | (d->g1p_bf16 ? NF_G1P_BF16 : 0);
+  if (d->dnh_bf16) f |= NF_DNH_BF16;
+  if (d->dgb) f |= NF_DGB | (d->dgb_bf16 ? NF_DGB_BF16 : 0) | (p.dbeta_in_place ? NF_DBETA_IN_PLACE : 0);
+  if (d->noise_z) f |= NF_NOISE;
+  if (d->x_up_channels > 0) f |= NF_UP;
+  if (d->dx_bf16) f |= NF_DX_BF16;
+  else if (d->dx_accumulate) f |= NF_DX_ACC;
+  return f;
+}
+
+// mixed-precision SPADE norm whose dout arrived in the dbeta half of [dgamma | dbeta] (1 + gamma in fp32 where the fused forward
+// kernel saved it, in bf16 where the dedicated gamma|beta kernel did) / PatchGAN's InstanceNorm + LeakyReLU
+constexpr int NF_SPADE = NF_DOUT_BF16 | NF_G1P | NF_DNH_BF16 | NF_DGB | NF_DGB_BF16 | NF_DBETA_IN_PLACE | NF_NOISE;
+constexpr int NF_IN_LRELU = (HRV_ACT_LRELU << NF_ACT_SHIFT) | NF_DNH_BF16;
+constexpr int NF_S2 = NF_DNH_BF16 | NF_NOISE;
+
+typedef void (*norm_s1_fn)(const NormBwdParams);
+typedef void (*norm_s2_fn)(const NormBwd2Params);
+typedef void (*norm_p1_fn)(const NormBwdParams, const NormBwdParams);
+typedef void (*norm_p2_fn)(const NormBwd2Params, const NormBwd2Params);
+template <class Fn> struct NormInst { int form; Fn fn; };
+#define S1(F) {F, norm_bwd_stage1_inst<F>}
+#define S2(F) {F, norm_bwd_stage2_inst<F>}
+#define P1(F) {F, norm_bwd2_stage1_inst<F>}
+#define P2(F) {F, norm_bwd2_stage2_inst<F>}
+static const NormInst<norm_s1_fn> norm_s1_insts[] = {S1(NF_SPADE | NF_G1P_BF16), S1(NF_SPADE | NF_G1P_BF16 | NF_UP), S1(NF_SPADE), S1(NF_IN_LRELU),
+                                                     S1(NF_IN_LRELU | NF_DOUT_BF16 | NF_OUT_BF16)};
+static const NormInst<norm_s2_fn> norm_s2_insts[] = {S2(NF_S2 | NF_DX_BF16), S2(NF_S2), S2(NF_S2 | NF_DX_ACC), S2(NF_S2 | NF_UP), S2(NF_S2 | NF_UP | NF_DX_ACC),
+                                                     S2(NF_DNH_BF16 | NF_DX_BF16)};
+static const NormInst<norm_p1_fn> norm_p1_insts[] = {P1(NF_SPADE | NF_G1P_BF16 | NF_UP), P1(NF_SPADE)};
+static const NormInst<norm_p2_fn> norm_p2_insts[] = {P2(NF_S2 | NF_UP), P2(NF_S2)};
+#undef S1
+#undef S2
+#undef P1
+#undef P2
+
+static bool norm_generic_forced() {
+  const char* e = hrv::env("HRV_NORM_BWD_GENERIC");
+  return e && atoi(e) != 0;
+}
+template <class Fn, size_t K>
+static Fn norm_inst_for(const NormInst<Fn> (&tab)[K], int form) {
+  if (!norm_generic_forced())
+    for (size_t i = 0; i < K; ++i)
+      if (tab[i].form == form) return tab[i].fn;
+  return nullptr;
+}
+
+static std::string norm_form_name(int f) {
+  static const struct { int bit; const char* name; } bits[] = {
+      {NF_DOUT_BF16, "dout_bf16"}, {NF_OUT_BF16, "out_bf16"}, {NF_G1P, "g1p"}, {NF_G1P_BF16, "g1p_bf16"}, {NF_DNH_BF16, "dnh_bf16"}, {NF_DGB, "dgb"},
+      {NF_DGB_BF16, "dgb_bf16"}, {NF_DBETA_IN_PLACE, "dbeta_in_place"}, {NF_NOISE, "noise"}, {NF_UP, "up"}, {NF_DX_BF16, "dx_bf16"}, {NF_DX_ACC, "dx_acc"}};
+  static const char* acts[] = {"", "relu", "lrelu", "tanh"};
+  std::string s = acts[(f & NF_ACT_MASK) >> NF_ACT_SHIFT];
+  for (const auto& b : bits)
+    if (f & b.bit) s += (s.empty() ? "" : "+") + std::string(b.name);
+  return s.empty() ? "plain" : s;
+}
+
+// the instance table as text, one line per kernel: "<single|pair>.<stage1|stage2> <form>" (DESIGN.md 7h lists the same lines)
+extern "C" const char* hrv_diag_norm_bwd_instances(void) {
+  static const std::string text = [] {
+    std::string t;
+    for (const auto& i : norm_s1_insts) t += "single.stage1 " + norm_form_name(i.form) + "\n";
+    for (const auto& i : norm_s2_insts) t += "single.stage2 " + norm_form_name(i.form) + "\n";
+    for (const auto& i : norm_p1_insts) t += "pair.stage1 " + norm_form_name(i.form) + "\n";
+    for (const auto& i : norm_p2_insts) t += "pair.stage2 " + norm_form_name(i.form) + "\n";
+    return t;
+  }();
+  return text.c_str();
+}
+
+static int norm_bwd2_check(const hrv_norm_bwd_t* a, const hrv_norm_bwd_t* b) {
+  int rc = norm_bwd_check(a);
+  if (rc) return rc;
+  rc = norm_bwd_check(b);
+  if (rc) return rc;
+  HRV_REQUIRE(a->x == b->x && a->x2 == b->x2 && a->x_cstride == b->x_cstride && a->x_coff == b->x_coff && a->x_up_channels == b->x_up_channels &&
+                  a->N == b->N && a->H == b->H && a->W == b->W && a->C == b->C,
+              "norm_bwd2: both norms must normalise the same x");
+  HRV_REQUIRE(!a->dx_bf16 && !a->dx_accumulate && a->workspace != b->workspace && a->dnh != b->dnh, "norm_bwd2: dx fp32 (written, = dx_a + dx_b); separate scratch");
+  return HRV_OK;
+}
+// the pair's kernels for two descriptors: an instance where both norms have the same form and that form is in the table
+static void norm_bwd2_route(const hrv_norm_bwd_t* a, const hrv_norm_bwd_t* b, const NormBwdParams& pa, const NormBwdParams& pb, norm_p1_fn& k1,
+                            norm_p2_fn& k2) {
+  const int fa = norm_form_of(a, pa), fb = norm_form_of(b, pb) & ~NF_DX_ACC & ~NF_DX_BF16;      // (b->dx is ignored)
+  k1 = (fa & NF_STAGE1) == (fb & NF_STAGE1) ? norm_inst_for(norm_p1_insts, fa & NF_STAGE1) : nullptr;
+  k2 = (fa & NF_STAGE2) == (fb & NF_STAGE2) ? norm_inst_for(norm_p2_insts, fa & NF_STAGE2) : nullptr;
+}
+
+// which kernels serve a descriptor (b == NULL) or a pair: bit 0 = stage 1 runs on an instance, bit 1 = stage 2; < 0: invalid
+extern "C" int hrv_diag_norm_bwd_route(const hrv_norm_bwd_t* a, const hrv_norm_bwd_t* b) {
+  const int rc = b ? norm_bwd2_check(a, b) : norm_bwd_check(a);
+  if (rc) return rc;
+  NormBwdParams pa, pb;
+  NormBwd2Params qa, qb;
+  float *m1, *m2;
+  norm_bwd_fill(a, pa, qa, m1, m2);
+  if (!b) {
+    const int f = norm_form_of(a, pa);
+    return (norm_inst_for(norm_s1_insts, f & NF_STAGE1) ? 1 : 0) | (norm_inst_for(norm_s2_insts, f & NF_STAGE2) ? 2 : 0);
+  }
+  norm_bwd_fill(b, pb, qb, m1, m2);
+  norm_p1_fn k1;
+  norm_p2_fn k2;
+  norm_bwd2_route(a, b, pa, pb, k1, k2);
+  return (k1 ? 1 : 0) | (k2 ? 2 : 0);
+}
+
+// Whether the pair pass is the faster way through norm_0 and norm_s of a block (gen_train.BlockT.backward asks; HRV_NORM_BWD2 there
+// overrides the answer).  The gate is on the form alone: both stages on an instance.  On the generic pair kernels (168 / 130
+// registers, three waves per SIMD) the pair lost 10-17 % to two sequential calls; on the instances (98 / 96 and 108 / 120, four
+// waves) it measured faster at every level of the 4 x 1024x768 step, 1024x768x80 (-27 %) down to 16x12x1040 (-41 %), and level
+// with them at 128x96x528 -- so there is no extent gate.
+extern "C" int hrv_spade_norm_bwd2_supported(const hrv_norm_bwd_t* a, const hrv_norm_bwd_t* b) {
+  if (norm_bwd2_check(a, b)) return 0;
+  return hrv_diag_norm_bwd_route(a, b) == 3 ? 1 : 0;
+}
+
 extern "C" int hrv_spade_norm_bwd_nhwc_f32(const hrv_norm_bwd_t* d, hrv_stream_t stream) {
   int rc = norm_bwd_check(d);
   if (rc) return rc;
@@ -1213,13 +1397,16 @@ extern "C" int hrv_spade_norm_bwd_nhwc_f32(const hrv_norm_bwd_t* d, hrv_stream_t
   NormBwd2Params q;
   float *m1, *m2;
   norm_bwd_fill(d, p, q, m1, m2);
-  hipLaunchKernelGGL(norm_bwd_stage1_kernel, dim3(nb, d->N, norm_chunks(C / 4)), dim3(256), 0, st, p);
+  const int form = norm_form_of(d, p);
+  const norm_s1_fn k1 = norm_inst_for(norm_s1_insts, form & NF_STAGE1);
+  const norm_s2_fn k2 = norm_inst_for(norm_s2_insts, form & NF_STAGE2);
+  hipLaunchKernelGGL(k1 ? k1 : norm_bwd_stage1_kernel, dim3(nb, d->N, norm_chunks(C / 4)), dim3(256), 0, st, p);
   rc = check_launch("norm_bwd_stage1_kernel");
   if (rc) return rc;
   hipLaunchKernelGGL(norm_bwd_finalize_kernel, dim3((d->N * C * 16 + 255) / 256), dim3(256), 0, st, p.part, d->N, nb, C, HW, m1, m2);
   rc = check_launch("norm_bwd_finalize_kernel");
   if (rc) return rc;
-  hipLaunchKernelGGL(norm_bwd_stage2_kernel, dim3(nb, d->N, norm_chunks(C / 4)), dim3(256), 0, st, q);
+  hipLaunchKernelGGL(k2 ? k2 : norm_bwd_stage2_kernel, dim3(nb, d->N, norm_chunks(C / 4)), dim3(256), 0, st, q);
   rc = check_launch("norm_bwd_stage2_kernel");
   if (rc) return rc;
   if (d->noise_z && d->dnoise_scale) {
@@ -1231,14 +1418,8 @@ extern "C" int hrv_spade_norm_bwd_nhwc_f32(const hrv_norm_bwd_t* d, hrv_stream_t
 }
 
 extern "C" int hrv_spade_norm_bwd2_nhwc_f32(const hrv_norm_bwd_t* a, const hrv_norm_bwd_t* b, hrv_stream_t stream) {
-  int rc = norm_bwd_check(a);
+  int rc = norm_bwd2_check(a, b);
   if (rc) return rc;
-  rc = norm_bwd_check(b);
-  if (rc) return rc;
-  HRV_REQUIRE(a->x == b->x && a->x2 == b->x2 && a->x_cstride == b->x_cstride && a->x_coff == b->x_coff && a->x_up_channels == b->x_up_channels &&
-                  a->N == b->N && a->H == b->H && a->W == b->W && a->C == b->C,
-              "norm_bwd2: both norms must normalise the same x");
-  HRV_REQUIRE(!a->dx_bf16 && !a->dx_accumulate && a->workspace != b->workspace && a->dnh != b->dnh, "norm_bwd2: dx fp32 (written, = dx_a + dx_b); separate scratch");
   const int HW = a->H * a->W, C = a->C;
   const int nb = norm_slabs(HW);
   hipStream_t st = (hipStream_t)stream;
@@ -1247,14 +1428,17 @@ extern "C" int hrv_spade_norm_bwd2_nhwc_f32(const hrv_norm_bwd_t* a, const hrv_n
   float *m1a, *m2a, *m1b, *m2b;
   norm_bwd_fill(a, pa, qa, m1a, m2a);
   norm_bwd_fill(b, pb, qb, m1b, m2b);
-  hipLaunchKernelGGL(norm_bwd2_stage1_kernel, dim3(nb, a->N, norm_chunks(C / 4)), dim3(256), 0, st, pa, pb);
+  norm_p1_fn k1;
+  norm_p2_fn k2;
+  norm_bwd2_route(a, b, pa, pb, k1, k2);
+  hipLaunchKernelGGL(k1 ? k1 : norm_bwd2_stage1_kernel, dim3(nb, a->N, norm_chunks(C / 4)), dim3(256), 0, st, pa, pb);
   rc = check_launch("norm_bwd2_stage1_kernel");
   if (rc) return rc;
   hipLaunchKernelGGL(norm_bwd_finalize_kernel, dim3((a->N * C * 16 + 255) / 256), dim3(256), 0, st, pa.part, a->N, nb, C, HW, m1a, m2a);
   hipLaunchKernelGGL(norm_bwd_finalize_kernel, dim3((a->N * C * 16 + 255) / 256), dim3(256), 0, st, pb.part, a->N, nb, C, HW, m1b, m2b);
   rc = check_launch("norm_bwd_finalize_kernel");
   if (rc) return rc;
-  hipLaunchKernelGGL(norm_bwd2_stage2_kernel, dim3(nb, a->N, norm_chunks(C / 4)), dim3(256), 0, st, qa, qb);
+  hipLaunchKernelGGL(k2 ? k2 : norm_bwd2_stage2_kernel, dim3(nb, a->N, norm_chunks(C / 4)), dim3(256), 0, st, qa, qb);
   rc = check_launch("norm_bwd2_stage2_kernel");
   if (rc) return rc;
   const hrv_norm_bwd_t* ds[2] = {a, b};

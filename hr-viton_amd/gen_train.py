@@ -371,7 +371,7 @@ class SpadeT:
         [dgamma | dbeta] by the data gradient that produces it, LeakyReLU derivative applied in that kernel's epilogue (mixed
         precision, dense channels): the normalisation backward then reads neither the activation output nor stores dbeta again --
         4 of its ~28 bytes per element.  Else None (HRV_DBETA_INPLACE=0: always None)."""
-        if (os.environ.get("HRV_DBETA_INPLACE", "1") == "0" or os.environ.get("HRV_NORM_BWD2", "0") != "0" or
+        if (os.environ.get("HRV_DBETA_INPLACE", "1") == "0" or
                 not T.MMA_BF16[0] or not want_bf16 or self.Cp != self.C or
                 self.C % 8 != 0 or not ctx["actv"].bf16 or not ctx["out"].bf16):
             return None
@@ -597,21 +597,30 @@ class BlockT:
         # that level's matrix-core tensors in bf16
         d_dx = self.n1.backward(ctx["n1"], d_h1, grads, None, False, dact_all.slice(hid * (k0 + 1), hid), dx_bf16=True, dgb=dgb1)
         d_h0, dgb0 = down(self.c0, d_dx, ctx["h0"], self.n0, ctx["n0"])
-        if (self.learned and ctx["n0"]["z"] is not None and ctx["ns"]["z"] is not None and not x.bf16 and
-                os.environ.get("HRV_NORM_BWD2", "0") != "0"):
-            # norm_0 and norm_s normalise the same x: one pass per stage over it, dx = dx_0 + dx_s written once (opt-in: bit-identical,
-            # 29 % fewer bytes -- and measured 10-17 % SLOWER than the two sequential calls at up_2..up_4: 168 / 132 registers leave
-            # three waves per SIMD where the single kernels keep four, and capping them at 128 spills)
-            d_hs = self.cs.backward(d_out, [(ctx["hs"], 0)], grads, dx_bf16=dh16 and ctx["hs"].bf16)
+        # norm_0 and norm_s normalise the same x: one pass per stage over it, dx = dx_0 + dx_s written once -- 32 instead of 48 bytes
+        # per element in mixed precision, bit-identical.  The library decides per form and extent (hrv_spade_norm_bwd2_supported:
+        # compiled instances that keep four waves per SIMD, and the levels the pair measured faster at);
+        # HRV_NORM_BWD2=0: never, =1: wherever the pair call is valid (the generic pair kernels hold 168 / 130 registers, three
+        # waves per SIMD, and measured 10-17 % SLOWER than the two calls at up_2..up_4)
+        mode = os.environ.get("HRV_NORM_BWD2", "")
+        d_hs = None
+        if self.learned and mode != "0" and ctx["n0"]["z"] is not None and ctx["ns"]["z"] is not None and not x.bf16:
+            d_hs, dgbs = down(self.cs, d_out, ctx["hs"], self.ns_, ctx["ns"])
             a0, as_ = self.n0.norm_args(ctx["n0"], d_h0), self.ns_.norm_args(ctx["ns"], d_hs)
-            d_x, dgb0, dgbs = T.norm_bwd2(x, a0, as_)
-            self.n0.after_norm(ctx["n0"], dgb0, a0["dnoise_scale"], grads, dact_all.slice(hid * k0, hid))
-            self.ns_.after_norm(ctx["ns"], dgbs, as_["dnoise_scale"], grads, dact_all.slice(0, hid))
-            self.shared_backward(ctx["segx"], dact_all, grads)
-            return d_x
+            for a, dgb in ((a0, dgb0), (as_, dgbs)):
+                if dgb is not None:
+                    a.update(act=ACT_NONE, out=None, dgb=dgb)
+            pair = T.norm_bwd2(x, a0, as_, only_where_faster=mode != "1")
+            if pair is not None:
+                d_x, dgb0, dgbs = pair
+                self.n0.after_norm(ctx["n0"], dgb0, a0["dnoise_scale"], grads, dact_all.slice(hid * k0, hid))
+                self.ns_.after_norm(ctx["ns"], dgbs, as_["dnoise_scale"], grads, dact_all.slice(0, hid))
+                self.shared_backward(ctx["segx"], dact_all, grads)
+                return d_x
         d_x = self.n0.backward(ctx["n0"], d_h0, grads, None, False, dact_all.slice(hid * k0, hid), dgb=dgb0)
         if self.learned:
-            d_hs, dgbs = down(self.cs, d_out, ctx["hs"], self.ns_, ctx["ns"])
+            if d_hs is None:      # (else the gate preferred two calls and d_hs / dgbs are already there)
+                d_hs, dgbs = down(self.cs, d_out, ctx["hs"], self.ns_, ctx["ns"])
             self.ns_.backward(ctx["ns"], d_hs, grads, d_x, True, dact_all.slice(0, hid), dgb=dgbs)
         else:
             T.add_slice(d_out, d_x, True)

@@ -861,6 +861,21 @@ def _norm_bwd_desc(x, mean, rstd, dout, act, slope, out, g1p, z, noise_scale, wa
     return d, dx, dgb, (dnh, ws)
 
 
+def _norm_bwd_bytes(d, in_place: bool, second_of_pair: bool = False) -> float:
+    """HBM bytes of the two stages of one normalisation backward in the form its descriptor asks for: 2-byte operands where they are
+    stored as bf16, no activation output without an activation, no dbeta store when ``dout`` already is the dbeta half.  The second
+    norm of a pair pass reads ``x`` with the first (twice) and adds into the one ``dx`` store.  (Reporting only: the GB/s of the
+    launch tables.  The [N][C] statistics, the slab partials and the noise plane are below a percent.)"""
+    w = lambda bf16: 2 if bf16 else 4
+    s1 = 4 + w(d.dout_bf16) + (w(d.out_bf16) if d.act != ACT_NONE else 0) + (w(d.g1p_bf16) if d.g1p else 0) + w(d.dnh_bf16)
+    if d.dgb:
+        s1 += w(d.dgb_bf16) * (1 if in_place else 2)
+    s2 = 4 + w(d.dnh_bf16) + w(d.dx_bf16) + (4 if d.dx_accumulate else 0)
+    if second_of_pair:
+        s1, s2 = s1 - 4, s2 - 4 - w(d.dx_bf16)
+    return float(d.N) * d.H * d.W * d.C * (s1 + s2)
+
+
 def norm_bwd(x: Act, mean: torch.Tensor, rstd: torch.Tensor, dout: Act, act: int = ACT_NONE, slope: float = 0.2,
              out: Optional[Act] = None, g1p: Optional[Act] = None, z: Optional[torch.Tensor] = None,
              noise_scale: Optional[torch.Tensor] = None, want_dgb: bool = False, dx: Optional[Act] = None,
@@ -870,9 +885,10 @@ def norm_bwd(x: Act, mean: torch.Tensor, rstd: torch.Tensor, dout: Act, act: int
     [dgamma | dbeta] in bf16 (mixed precision: only the gamma|beta conv's matrix-core backward reads it).  ``dgb``: the
     [dgamma | dbeta] tensor allocated by the caller whose dbeta half ``dout`` is (norm_bwd_dgb / the header's "dbeta in place")."""
     lib = _lib.load()
+    in_place = dgb is not None
     d, dx, dgb, _keep = _norm_bwd_desc(x, mean, rstd, dout, act, slope, out, g1p, z, noise_scale, want_dgb, dx, dx_accumulate, dnoise_scale,
                                        dns_accumulate, dgb_bf16, dx_bf16, dgb)
-    with _Timed("norm_bwd", "spade_norm_bwd", 0.0, 4.0 * x.N * x.H * x.W * x.Cp * (7 + (2 if want_dgb else 0))):
+    with _Timed("norm_bwd", "spade_norm_bwd", 0.0, _norm_bwd_bytes(d, in_place)):
         _lib.check(lib.hrv_spade_norm_bwd_nhwc_f32(C.byref(d), _stream()), "hrv_spade_norm_bwd_nhwc_f32")
     return dx, dgb
 
@@ -885,19 +901,29 @@ def norm_bwd_dgb(x: Act, bf16: bool) -> Tuple[Act, Act]:
     return dgb, dgb.slice(x.Cp, x.C)
 
 
-def norm_bwd2(x: Act, a: dict, b: dict):
+def norm_bwd2(x: Act, a: dict, b: dict, only_where_faster: bool = False):
     """Two normalisations of the same x in one pass per stage (hrv_spade_norm_bwd2_nhwc_f32): ``a`` / ``b`` hold the keyword
-    arguments of norm_bwd except x / dx / dx_accumulate.  Returns (dx = dx_a + dx_b (fp32), dgb_a, dgb_b)."""
+    arguments of norm_bwd except x / dx / dx_accumulate.  Returns (dx = dx_a + dx_b (fp32), dgb_a, dgb_b) -- or, with
+    ``only_where_faster``, None without launching anything where the library's gate (hrv_spade_norm_bwd2_supported: the form has
+    compiled instances and the extent is one the pair pass wins at) prefers the two sequential calls."""
     lib = _lib.load()
     da, dx, dgb_a, _ka = _norm_bwd_desc(x, a["mean"], a["rstd"], a["dout"], a.get("act", ACT_NONE), a.get("slope", 0.2), a.get("out"), a.get("g1p"),
                                         a.get("z"), a.get("noise_scale"), a.get("want_dgb", False), None, False, a.get("dnoise_scale"),
-                                        a.get("dns_accumulate", False), a.get("dgb_bf16", False), False)
+                                        a.get("dns_accumulate", False), a.get("dgb_bf16", False), False, a.get("dgb"))
     db, _, dgb_b, _kb = _norm_bwd_desc(x, b["mean"], b["rstd"], b["dout"], b.get("act", ACT_NONE), b.get("slope", 0.2), b.get("out"), b.get("g1p"),
                                        b.get("z"), b.get("noise_scale"), b.get("want_dgb", False), dx, False, b.get("dnoise_scale"),
-                                       b.get("dns_accumulate", False), b.get("dgb_bf16", False), False)
-    with _Timed("norm_bwd", "spade_norm_bwd x2", 0.0, 4.0 * x.N * x.H * x.W * x.Cp * (10 + 2 * (a.get("want_dgb", False) + b.get("want_dgb", False)))):
+                                       b.get("dns_accumulate", False), b.get("dgb_bf16", False), False, b.get("dgb"))
+    if only_where_faster and not lib.hrv_spade_norm_bwd2_supported(C.byref(da), C.byref(db)):
+        return None
+    nbytes = _norm_bwd_bytes(da, a.get("dgb") is not None) + _norm_bwd_bytes(db, b.get("dgb") is not None, second_of_pair=True)
+    with _Timed("norm_bwd", "spade_norm_bwd x2", 0.0, nbytes):
         _lib.check(lib.hrv_spade_norm_bwd2_nhwc_f32(C.byref(da), C.byref(db), _stream()), "hrv_spade_norm_bwd2_nhwc_f32")
     return dx, dgb_a, dgb_b
+
+
+def norm_bwd_instances():
+    """The compile-time instances of the normalisation-backward kernels, as the library lists them: ["single.stage1 <form>", ...]"""
+    return _lib.load().hrv_diag_norm_bwd_instances().decode().splitlines()
 
 
 LOSS_L1, LOSS_HINGE_D_FAKE, LOSS_HINGE_D_REAL, LOSS_NEG_MEAN, LOSS_MSE = 0, 1, 2, 3, 4

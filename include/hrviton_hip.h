@@ -321,6 +321,18 @@ int hrv_spade_norm_bwd_nhwc_f32(const hrv_norm_bwd_t* d, hrv_stream_t stream);
  * pass per stage: x is read once, a->dx <- dx_a + dx_b is written once (b->dx is ignored); everything else per descriptor.
  * Bit-identical to hrv_spade_norm_bwd_nhwc_f32(a) followed by (b with dx = a->dx, dx_accumulate = 1). */
 int hrv_spade_norm_bwd2_nhwc_f32(const hrv_norm_bwd_t* a, const hrv_norm_bwd_t* b, hrv_stream_t stream);
+/* Compile-time instances.  Both entry points above pick, per stage, a kernel compiled for the descriptor's storage form (which
+ * operands are bf16, whether there is noise, an activation, 1 + gamma, [dgamma | dbeta], dbeta in place, an up-sampled source,
+ * how dx is stored) where that form is in the library's table, and the generic run-time kernel otherwise or when
+ * HRV_NORM_BWD_GENERIC=1; results are bit-identical either way.
+ * hrv_diag_norm_bwd_instances: the table, one "<single|pair>.<stage1|stage2> <form>" line per kernel.
+ * hrv_diag_norm_bwd_route(a, b or NULL): bit 0 = stage 1 of this descriptor (pair) runs on an instance, bit 1 = stage 2; < 0: the
+ *   descriptor is refused.
+ * hrv_spade_norm_bwd2_supported(a, b): 1 where the one-pass pair is the faster form for these two descriptors (both stages on an
+ *   instance; measured per level), 0 where two sequential calls are, or the pair is not valid. */
+const char* hrv_diag_norm_bwd_instances(void);
+int hrv_diag_norm_bwd_route(const hrv_norm_bwd_t* a, const hrv_norm_bwd_t* b);
+int hrv_spade_norm_bwd2_supported(const hrv_norm_bwd_t* a, const hrv_norm_bwd_t* b);
 /* Loss value + gradient in one pass.  mode 0: L1 |a-b| (feature matching / VGG,
  * train_generator.py:300-312); 1: hinge-D fake max(1+a,0); 2: hinge-D real max(1-a,0);
  * 3: -a (generator hinge) (network_generator.py:365-376); 4: (a-b)^2 (LSGAN, networks.py:258-299).
