@@ -295,9 +295,9 @@ class SpadeT:
         else:
             mean, rstd = ops.instnorm_stats(x, zz, ns if zz is not None else None)
         mb = T.MMA_BF16[0]     # mixed precision: bf16 matrix cores, fp32 epilogue / statistics / x
-        cfg = ((8 if self.G % 2 == 0 else 9) if mb else self.cfg)
-        if mb:                 # bf16 actv: each tile's halo patch stays in LDS (ops.patch_tile)
-            cfg = ops.patch_tile(actv.bf16, 3, 3, 1, 1, 1, 0, self.hid, self.G * 64, x.N, x.H, x.W, wide=True) or cfg
+        # (bf16 actv: each tile's halo patch stays in LDS where ops.patch_tile has a tile)
+        cfg = ops.engine_tile("mb", 0, self.G * 64, mb and actv.bf16, 3, 3, 1, 1, 1, 0, self.hid, x.N, x.H, x.W, wide=True,
+                              base=None if mb else self.cfg)
         out_bf16 = mb and actv.bf16 and self.C % 8 == 0
         if (mb and actv.bf16 and out_bf16 and x.cstride % 4 == 0 and
                 T.spade_gb_ok(0, self.C, self.Cp, self.hid, x.N, x.H, x.W)):

@@ -18,6 +18,7 @@ import torch
 
 from . import _lib
 from ._lib import ACT_LRELU, ACT_NONE, ACT_RELU, ACT_TANH, HrvError  # noqa: F401
+from .conv_dispatch import _cpad, engine_tile, patch_tile  # noqa: F401  (patch_tile: the name tests and tools ask)
 
 
 # bumped by hr_viton_amd.optim.Adam.step(): the fused Adam kernel writes parameters through raw
@@ -35,45 +36,6 @@ def weights_epoch(tensors) -> int:
 
 def _ceil4(c: int) -> int:
     return (c + 3) // 4 * 4
-
-
-def _cpad(c: int, bf16: bool) -> int:
-    """Channel padding of an NHWC tensor: one 16-byte gather group (4 fp32 / 8 bf16 channels)."""
-    return (c + 7) // 8 * 8 if bf16 else (c + 3) // 4 * 4
-
-
-def patch_tile(bf16_sources: bool, KH: int, KW: int, stride: int, pad: int, nsrc: int, up: int, C: int, cols: int,
-               N: int, H: int, W: int, wide: bool = False) -> int:
-    """Patch-mode tile of the conv engine (conv_f32.hip, VAR bit 6) for this layer, or 0.  Patch mode: 3x3 stride-1
-    'same' convolution over ONE bf16-stored source with C % 128 == 0; the 8x16-pixel tile keeps its 10x18 halo
-    patch resident in LDS and only the weight tiles stream (the implicit-GEMM gather re-reads every activation
-    pixel from L2 once per tap).  tile_cfg 17: 128 columns, 18: 64 columns (column counts that are odd multiples
-    of 64 -- the SPADE gamma|beta convs of the 80/144/272-channel blocks).  Needs enough tiles to fill the chip
-    (else the gather tiles with split-K win).  HRV_CONV_PATCH=0 disables it, =16 selects the 16x16-pixel tile."""
-    env = os.environ.get("HRV_CONV_PATCH", "1")
-    if not (bf16_sources and KH == 3 and KW == 3 and stride == 1 and pad == 1 and nsrc == 1 and up == 0 and
-            C % 128 == 0 and env != "0"):
-        return 0
-    # tile_cfg 19 (conv_patchw.hip): 16x16-pixel tiles x up to 192 columns per block, one block per CU, weights
-    # streamed once per 256 pixels through 3 LDS stages.  Opt-in (HRV_CONV_PATCHW=1): measured in the training step
-    # it is 5-10 % SLOWER than the 8x16 tiles below (up_4 gamma|beta 2.42 vs 2.25 ms) -- with one block per CU nothing
-    # overlaps the SPADE epilogue's 246 KB of loads/stores per tile, which the two resident blocks of cfg 17/18 hide.
-    # (``wide``: the caller's epilogue is one conv_patchw.hip implements -- the SPADE modulate sites)
-    if wide and os.environ.get("HRV_CONV_PATCHW", "0") != "0" and N * ((H + 15) // 16) * ((W + 15) // 16) >= 256:
-        return 19
-    c64 = (cols + 63) // 64
-    if c64 * 64 - cols > 32:
-        return 0
-    wide = c64 % 2 == 0
-    if N * ((H + 7) // 8) * ((W + 15) // 16) * (c64 // 2 if wide else c64) < 512:
-        return 0
-    if env == "16" and wide:
-        return 16
-    return 17 if wide else 18
-
-
-def patch_tile_ok(*a) -> bool:
-    return patch_tile(*a) != 0
 
 
 def _stream() -> int:
@@ -368,20 +330,8 @@ class ConvLayer:
             s.up_shift, s.pre_act, s.C_real = up, pre, self.src_real[i]
         naive = os.environ.get("HRV_CONV_IMPL", "mfma") == "naive"
         if cfg is None:
-            cfg = lib.hrv_conv2d_pick_tile(N * Ho * Wo, self.Cout)
-            if self.mixed:      # 128-byte-row tile with the least column padding (cfg 8: 128 columns, 9: 64)
-                cfg = 8 if (self.Cout + 127) // 128 * 128 <= (self.Cout + 63) // 64 * 64 else 9
-            if self.bf16 and cfg in (0, 6):
-                # 128-byte K-tile rows: 128x128 tile +15-20 % (profiles/r01_conv_bench_bf16_rb.txt); the 128x64 tile
-                # additionally stages its operands by LDS-DMA (profiles/r01_conv_bench_bf16_glds.txt)
-                cfg = 8 if cfg == 0 else 9
-            if self.bf16 and self.KH == 1 and self.KW == 1 and sum(self.src_pad) <= 128 and self.Cout % 64 == 0:
-                # one or two K-tiles (conv_shared as a 1x1 over the 72 expanded taps): the block is all prologue and
-                # epilogue, so the small 128x64 tile with 64-byte rows wins on resident blocks (0.39 vs 0.48 ms)
-                cfg = 6
-            pt = patch_tile(self.bf16, self.KH, self.KW, self.stride, self.pad, len(specs), up0, self.src_pad[0],
-                            self.Cout, N, H, W)
-            cfg = pt or cfg
+            cfg = engine_tile("mb" if self.mixed else "serve", N * Ho * Wo, self.Cout, self.bf16, self.KH, self.KW, self.stride,
+                              self.pad, len(specs), up0, self.src_pad[0], N, H, W, c1x1=sum(self.src_pad))
         forced = os.environ.get("HRV_CONV_TILE") if (spade is None and not self.mixed) else None
         if forced is not None:
             cfg = int(forced)
@@ -585,8 +535,7 @@ class SpadeModulate:
                 T.spade_gb_forward(actv, x, mean, rstd, z if use_noise else None, self.ns if use_noise else None, pk, bg, bb,
                                    self.conv.act, self.conv.slope, out, None, self.conv.name, self.flops(x.N, x.H, x.W), nb)
                 return out
-        cfg = self.cfg
-        cfg = patch_tile(self.bf16, 3, 3, 1, 1, 1, 0, actv.Cp, self.conv.Cout, x.N, x.H, x.W, wide=True) or cfg
+        cfg = engine_tile("serve", 0, self.conv.Cout, self.bf16, 3, 3, 1, 1, 1, 0, actv.Cp, x.N, x.H, x.W, wide=True, base=self.cfg)
         return self.conv([actv], out=out, spade=e, out_channels=self.Creal, cfg=cfg)
 
 

@@ -11,20 +11,9 @@ from typing import Optional, Sequence, Tuple
 import torch
 
 from . import _lib, ops
+from .conv_dispatch import (COUT1, MMA_BF16, P2, THIN, conv_p2_ok, plan_dgrad, plan_forward,  # noqa: F401  (MMA_BF16, conv_p2_ok: used
+                            plan_wgrad)                                                        # through this module by callers)
 from .ops import ACT_LRELU, ACT_NONE, ACT_RELU, Act, _ceil4, _stream, _Timed, _workspace
-
-
-# Mixed-precision training switch (the reference's --fp16 / apex-O1 role): when on, every training
-# convolution (forward and data gradient) rounds its fp32 operands to bf16 while staging them and runs on
-# v_mfma_f32_32x32x16_bf16 with fp32 accumulation; all tensors in HBM, the epilogues, the normalisations,
-# the losses and the optimizer stay fp32.  The weight gradient has its own switch-aware kernel.
-MMA_BF16 = [False]
-
-
-def _bf16_tile(cout: int) -> int:
-    """128-byte-row tile of the bf16 engine with the least column padding (cfg 8: 128 columns, cfg 9: 64)."""
-    p64, p128 = (cout + 63) // 64 * 64, (cout + 127) // 128 * 128
-    return 8 if p128 <= p64 else 9
 
 
 _FROZEN_PACKS: dict = {}
@@ -462,15 +451,6 @@ def _run_engine(srcs, w_packed, Cout, cfg, N, H, W, Ho, Wo, KH, KW, stride, pad_
     return out
 
 
-def _thin_ok(a: Act, KH: int, KW: int, stride: int, pad: int, cols: int, N: int, H: int, W: int) -> bool:
-    """thin_conv.hip serves this layer: mixed precision, ONE bf16-stored source read at its own resolution, 3x3 / 1x1
-    stride-1 'same', <= 96 channels on either side (the 1024x768 level), enough pixels for a persistent grid."""
-    import os
-    return (MMA_BF16[0] and a.bf16 and stride == 1 and KH == KW and pad == KH // 2 and N * H * W >= 65536 and
-            os.environ.get("HRV_THIN_CONV", "1") != "0" and
-            bool(_lib.load().hrv_thin_conv_supported(KH, KW, a.Cp, cols)))
-
-
 def _thin_conv(src: Act, w: torch.Tensor, mode: int, sigma, wscale: float, shift, residual: Optional[Act], res_mode: int,
                act: int, slope: float, out: Act, name: str, flops: float):
     lib = _lib.load()
@@ -492,19 +472,6 @@ def _thin_conv(src: Act, w: torch.Tensor, mode: int, sigma, wscale: float, shift
     return out
 
 
-def _cout1_ok(w: torch.Tensor, x: Act, stride: int, pad: int, part: str = "fwd") -> bool:
-    """conv_cout1.hip serves this layer: ONE output channel, K <= 4, stride 1, pad >= (K-1)/2, an fp32 source with 4-channel
-    granules (PatchGAN's last convolution).  HRV_CONV_COUT1: "0" off, "fwd" the forward kernel only, default all three.
-    Measured at 2 x 4 x 131 x 99 x 256: forward 0.233 -> 0.109 ms; the first data- / weight-gradient kernels (16 global dY
-    loads per pixel) were no faster than the padded matrix-core path (0.099 / 0.72 ms against 0.094 / 0.19) and were
-    rewritten with the dY rows of an input row staged in LDS."""
-    Cout, cin, KH, KW = w.shape
-    mode = os.environ.get("HRV_CONV_COUT1", "1")
-    return (Cout == 1 and KH == KW and KH <= 4 and stride == 1 and 0 <= pad < KH and 2 * pad >= KH - 1 and not x.bf16 and
-            x.C == cin and cin % 4 == 0 and cin <= 2048 and x.cstride % 4 == 0 and x.coff % 4 == 0 and w.is_contiguous() and
-            mode != "0" and (mode != "fwd" or part == "fwd"))
-
-
 def _cout1_desc(w, x: Act, pad: int, wscale: float, sigma, y: Act):
     d = _lib.hrv_conv_cout1_t()
     d.x, d.N, d.H, d.W, d.C, d.x_cstride, d.x_coff = x.t.data_ptr(), x.N, x.H, x.W, x.C, x.cstride, x.coff
@@ -515,35 +482,6 @@ def _cout1_desc(w, x: Act, pad: int, wscale: float, sigma, y: Act):
     return d
 
 
-_ALT_F32_TILE = {0: 7, 6: 4, 1: 2, 5: 3}      # 128-row fp32 tiles -> the 256-row tile of the same width
-
-
-def _f32_tile(M: int, cout: int) -> int:
-    """fp32-engine tile of a training convolution: hrv_conv2d_pick_tile, or -- HRV_CONV_TILE_TRAIN=bm256, a TEST knob -- the
-    256-row tile of the same width (another block shape, wave layout and split-K geometry for the same convolution: the
-    at-size self-consistency check of tests/test_gpu_fullsize_tocg.py)."""
-    cfg = _lib.load().hrv_conv2d_pick_tile(M, cout)
-    if os.environ.get("HRV_CONV_TILE_TRAIN") == "bm256":
-        cfg = _ALT_F32_TILE.get(cfg, cfg)
-    return cfg
-
-
-def _p2_fwd_ok(w: torch.Tensor, a0: Act, stride: int, pad: int, out: Optional[Act], out_is_bf16: bool, residual, act: int) -> bool:
-    """csrc/conv_p2.hip serves this forward layer: 3x3 stride-1 'same' over ONE bf16-stored source read at its own resolution."""
-    Cout, cin, KH, KW = w.shape
-    oal = 8 if out_is_bf16 else 4
-    # a K that is not a multiple of 16 or a column count off the 16-byte store granule: only where it was measured to win -- a
-    # 3-channel image into >= 64 columns (VGG19 features.0: the thin kernel's tile loop is latency-bound there)
-    odd = cin % 16 != 0 or cin < 32 or Cout % oal != 0
-    return ((KH, KW, stride, pad) == (3, 3, 1, 1) and act in (ACT_NONE, ACT_RELU, ACT_LRELU) and a0.bf16 and a0.C == cin and
-            (not odd or (Cout >= 64 and Cout % oal == 0 and os.environ.get("HRV_CONV_P2_ODD", "1") != "0")) and
-            a0.cstride % 8 == 0 and a0.coff % 8 == 0 and a0.coff + (cin + 7) // 8 * 8 <= a0.cstride and w.is_contiguous() and
-            (out is None or (out.cstride % oal == 0 and out.coff % oal == 0)) and
-            (residual is None or (type(residual) is Act and residual.C == Cout and residual.cstride % 4 == 0 and residual.coff % 4 == 0 and
-                                  residual.t.data_ptr() % 16 == 0)) and
-            conv_p2_ok(cin, Cout, a0.N, a0.H, a0.W))
-
-
 def conv_forward_fast(w: torch.Tensor, a0: Act, pad: int, wscale: float, shift: Optional[torch.Tensor], residual: Optional[Act], act: int,
                       slope: float, out: Optional[Act], out_bf16: bool, name: str, frozen) -> Optional[Act]:
     """bf16 SERVING plans (network_generator): a stride-1 layer over one bf16-stored source on conv_p2.hip or thin_conv.hip when one
@@ -552,77 +490,51 @@ def conv_forward_fast(w: torch.Tensor, a0: Act, pad: int, wscale: float, shift: 
     packed stream is cached under it)."""
     if os.environ.get("HRV_SERVE_FAST", "1") == "0" or not a0.bf16:
         return None
-    Cout, cin, KH, KW = w.shape
-    prev = MMA_BF16[0]
-    MMA_BF16[0] = True
-    try:
-        bf = out.bf16 if out is not None else (out_bf16 and Cout % 8 == 0)
-        if not (_p2_fwd_ok(w, a0, 1, pad, out, bf, residual, act) or
-                (w.is_contiguous() and a0.C == cin and _thin_ok(a0, KH, KW, 1, pad, Cout, a0.N, a0.H, a0.W) and
-                 (out is None or out.cstride % 4 == 0))):
-            return None
-        return conv_forward_dev(w, [(a0, 0)], 1, pad, wscale=wscale, shift=shift, residual=residual, act=act, slope=slope, out=out,
-                                name=name, out_bf16=out_bf16, frozen=frozen)
-    finally:
-        MMA_BF16[0] = prev
+    p = plan_forward(w, [(a0, 0)], 1, pad, residual, act, out, 0, out_bf16, mb=True)     # (the gates answer as in training)
+    if p.kernel not in (P2, THIN):
+        return None
+    return conv_forward_dev(w, [(a0, 0)], 1, pad, wscale=wscale, shift=shift, residual=residual, act=act, slope=slope, out=out,
+                            name=name, out_bf16=out_bf16, frozen=frozen, plan=p)
 
 
 def conv_forward_dev(w: torch.Tensor, srcs: Sequence[Tuple[Act, int]], stride: int, pad: int, wscale: float = 1.0,
                      sigma: Optional[torch.Tensor] = None, shift: Optional[torch.Tensor] = None, residual: Optional[Act] = None, act: int = ACT_NONE,
                      slope: float = 0.2, out: Optional[Act] = None, out_up: int = 0, name: str = "conv",
-                     out_bf16: bool = False, frozen=None, batch=None) -> Act:
+                     out_bf16: bool = False, frozen=None, batch=None, plan=None) -> Act:
     """Forward convolution with device-resident, per-step packed weights.  ``srcs``: (Act, up_shift).
-    ``out_bf16`` (mixed precision only): store the result in bf16 -- for tensors that only matrix cores read."""
+    ``out_bf16`` (mixed precision only): store the result in bf16 -- for tensors that only matrix cores read.
+    ``plan``: conv_dispatch.plan_forward's answer for these very operands, where the caller has asked already."""
+    p = plan or plan_forward(w, srcs, stride, pad, residual, act, out, out_up, out_bf16)
     lib = _lib.load()
     Cout, cin, KH, KW = w.shape
     a0, up0 = srcs[0]
     N = a0.N
     H, W = (a0.H << up0, a0.W << up0) if up0 >= 0 else (a0.H >> -up0, a0.W >> -up0)
     Ho, Wo = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
-    mb = MMA_BF16[0]
-    if (len(srcs) == 1 and up0 == 0 and out_up == 0 and residual is None and act == ACT_NONE and out is None and
-            _cout1_ok(w, a0, stride, pad)):
-        out = ops.alloc(N, Ho, Wo, 1, a0.t.device)          # (pad channels 1..3 are zero)
+    fl = 2.0 * N * Ho * Wo * Cout * cin * KH * KW
+    if out is None and p.kernel in (COUT1, THIN, P2):          # (the generic engine packs first, as it always has)
+        out = ops.alloc(N, Ho, Wo, Cout, a0.t.device, bf16=p.out_bf16)
+    if p.kernel == COUT1:
         d = _cout1_desc(w, a0, pad, wscale, sigma, out)
         d.bias = None if shift is None else shift.data_ptr()
-        with _Timed("conv", name, 2.0 * N * Ho * Wo * cin * KH * KW, ops.act_bytes(a0) + 4.0 * N * Ho * Wo, "cout1_kernel"):
+        with _Timed("conv", name, fl, ops.act_bytes(a0) + 4.0 * N * Ho * Wo, COUT1):
             _lib.check(lib.hrv_conv_cout1_fwd_f32(C.byref(d), _stream()), f"hrv_conv_cout1_fwd_f32[{name}]")
         return out
-    p2_bf = out.bf16 if out is not None else (out_bf16 and Cout % 8 == 0)
-    p2 = mb and len(srcs) == 1 and up0 == 0 and out_up == 0 and _p2_fwd_ok(w, a0, stride, pad, out, p2_bf, residual, act)
-    if p2 and os.environ.get("HRV_CONV_P2_WIDE", "1") == "0":      # A/B: the kernel's round-4 mid range (64-column multiples, thin kernel first)
-        p2 = (Cout % 64 == 0 and residual is None and
-              not _thin_ok(a0, KH, KW, stride, pad, Cout, N, H, W))
-    if (not p2 and len(srcs) == 1 and up0 == 0 and out_up == 0 and w.is_contiguous() and
-            _thin_ok(a0, KH, KW, stride, pad, Cout, N, H, W) and (out is None or out.cstride % 4 == 0)):
+    if p.kernel == THIN:
         assert a0.C == cin, (name, a0.C, cin)
-        if out is None:
-            out = ops.alloc(N, Ho, Wo, Cout, a0.t.device, bf16=out_bf16 and Cout % 4 == 0)
-        return _thin_conv(a0, w, 0, sigma, wscale, shift, residual, 0, act, slope, out, name,
-                          2.0 * N * Ho * Wo * Cout * cin * KH * KW)
-    if p2:
-        # plain 3x3 over one bf16 source: the two-blocks-per-CU kernel (VGG19's 128..512-channel layers; SPADEResBlock.conv_0 of
-        # up_2 / up_3: 272 -> 128, 144 -> 64)
-        if out is None:
-            out = ops.alloc(N, Ho, Wo, Cout, a0.t.device, bf16=p2_bf)
+        return _thin_conv(a0, w, 0, sigma, wscale, shift, residual, 0, act, slope, out, name, fl)
+    if p.kernel == P2:
         pk = conv_p2_pack(0, w, None, cin, Cout, sigma, wscale, frozen)
-        return conv_p2(a0, pk, Cout, out, bias=shift, act=act, slope=slope, residual=residual, name=name,
-                       flops=2.0 * N * Ho * Wo * Cout * cin * 9, variant="mode 0")
-    cfg = _bf16_tile(Cout) if mb else _f32_tile(N * Ho * Wo, Cout)
-    if mb:                 # bf16-stored source: the halo patch stays in LDS (ops.patch_tile)
-        if KH == 1 and KW == 1 and a0.bf16 and len(srcs) == 1 and a0.Cp <= 128 and Cout % 64 == 0:
-            cfg = 6        # one or two K-tiles: the small tile with 64-byte rows keeps more blocks resident
-        cfg = ops.patch_tile(a0.bf16, KH, KW, stride, pad, len(srcs), up0, a0.Cp, Cout, N, H, W) or cfg
+        return conv_p2(a0, pk, Cout, out, bias=shift, act=act, slope=slope, residual=residual, name=name, flops=fl, variant=p.variant)
     real = [a.C for a, _ in srcs]
     assert sum(real) == cin, (name, real, cin)
-    packed, _ = pack_weight_dev(w, [a.Cp for a, _ in srcs], real, cfg, 0, stride, pad, wscale=wscale, sigma=sigma,
-                                bf16=mb, frozen=frozen, batch=batch)
+    packed, _ = pack_weight_dev(w, [a.Cp for a, _ in srcs], real, p.cfg, 0, stride, pad, wscale=wscale, sigma=sigma,
+                                bf16=p.mb, frozen=frozen, batch=batch)
     if out is None:
-        out = ops.alloc(N, Ho << out_up, Wo << out_up, Cout, a0.t.device, bf16=out_bf16 and mb)
-    fl = 2.0 * N * Ho * Wo * Cout * cin * KH * KW
-    return _run_engine([(a, up, a.C) for a, up in srcs], packed, Cout, cfg, N, H, W, Ho, Wo, KH, KW, stride, pad, pad,
+        out = ops.alloc(N, Ho << out_up, Wo << out_up, Cout, a0.t.device, bf16=p.out_bf16)
+    return _run_engine([(a, up, a.C) for a, up in srcs], packed, Cout, p.cfg, N, H, W, Ho, Wo, KH, KW, stride, pad, pad,
                        out, shift=shift, residual=residual, act=act, slope=slope, out_up=out_up, name=name, flops=fl,
-                       mma_bf16=mb)
+                       mma_bf16=p.mb)
 
 
 def conv_dgrad(dy: Act, w, H: int, W: int, stride: int, pad: int, wscale: float = 1.0,
@@ -635,12 +547,13 @@ def conv_dgrad(dy: Act, w, H: int, W: int, stride: int, pad: int, wscale: float 
     ``add`` (instead of ``act_mask``): a second gradient of the same tensor, summed in the epilogue (the feature-matching
     tap gradient of a PatchGAN feature joins the gradient flowing down through it: no separate accumulation pass).
     ``add_after`` (with or without ``act_mask``): a gradient w.r.t. the same PRE-activation, added behind the mask (VGG19's tap
-    gradients, which carry their ReLU derivative already) -- in the epilogue of csrc/conv_p2.hip where that kernel serves the layer,
-    else by a separate add_slice pass."""
+    gradients, which carry their ReLU derivative already) -- in the epilogue of csrc/conv_p2.hip where that kernel serves the layer
+    and the addend can ride (the plan's ``ride``), else by a separate add_slice pass."""
     lib = _lib.load()
     if add_after is not None:
         assert add is None and (add_after.N, add_after.H, add_after.W) == (dy.N, H, W)
     assert add is None or act_mask is None, "conv_dgrad: one residual slot (mask or addend)"
+    p = plan_dgrad(dy, w, H, W, stride, pad, act_mask, out, out_bf16, add, add_after)
     pair = w if isinstance(w, (tuple, list)) else None
     if pair is not None:
         assert stride == 1 and sigma is None and wscale == 1.0
@@ -650,74 +563,42 @@ def conv_dgrad(dy: Act, w, H: int, W: int, stride: int, pad: int, wscale: float 
         Cout, cin, KH, KW = w.shape
     N, Ho, Wo = dy.N, dy.H, dy.W
     assert dy.C == Cout
-    mb = MMA_BF16[0]
+    mb = p.mb
     if out is None:
-        out = ops.alloc(N, H, W, cin, dy.t.device, bf16=out_bf16 and mb and cin % 8 == 0 and stride == 1)
-    cfg = _bf16_tile(cin) if mb else _f32_tile(N * H * W, cin)
+        out = ops.alloc(N, H, W, cin, dy.t.device, bf16=p.out_bf16)
     res_mode = 1 if act_mask is not None else 0
-    if add is not None:
-        act_mask = add           # (the engine's residual slot: res_mode 0 adds it)
+    res = act_mask if add is None else add           # (the engine's residual slot: res_mode 0 adds it)
     fl = 2.0 * N * Ho * Wo * Cout * cin * KH * KW
-    if (pair is None and res_mode == 0 and not dy.bf16 and not out.bf16 and (add is None or not add.bf16) and
-            (Ho, Wo) == (H + 2 * pad - KH + 1, W + 2 * pad - KW + 1) and _cout1_ok(w, Act(out.t, cin, out.coff), stride, pad, "dgrad")):
+    if p.kernel == COUT1:
         d = _cout1_desc(w, Act(out.t, cin, out.coff), pad, wscale, sigma, dy)      # (x slot: geometry only)
         d.dx, d.dx_cstride, d.dx_coff = out.t.data_ptr(), out.cstride, out.coff
         if add is not None:
             d.add, d.add_cstride, d.add_coff = add.t.data_ptr(), add.cstride, add.coff
-        with _Timed("conv", name, fl, ops.act_bytes(out) * (2 if add is not None else 1) + 4.0 * N * Ho * Wo, "cout1_kernel"):
+        with _Timed("conv", name, fl, ops.act_bytes(out) * (2 if add is not None else 1) + 4.0 * N * Ho * Wo, COUT1):
             _lib.check(lib.hrv_conv_cout1_dgrad_f32(C.byref(d), _stream()), f"hrv_conv_cout1_dgrad_f32[{name}]")
-        return out
-    oal = 8 if out.bf16 else 4
-    # (columns off the 16-byte store granule: only the >= 64-channel gradient into a 3-channel image, VGG19 features.0 -- the padded
-    #  lanes of `out` receive zeros)
-    p2 = (mb and stride == 1 and (KH, KW, pad) == (3, 3, 1) and (Ho, Wo) == (H, W) and dy.bf16 and add is None and dy.C == Cout and
-          Cout % 16 == 0 and dy.cstride % 8 == 0 and dy.coff % 8 == 0 and
-          (cin % oal == 0 or (pair is None and Cout >= 64 and out.coff + (cin + oal - 1) // oal * oal <= out.cstride and
-                              os.environ.get("HRV_CONV_P2_ODD", "1") != "0")) and
-          out.cstride % oal == 0 and out.coff % oal == 0 and
-          (act_mask is None or (act_mask.bf16 and act_mask.C == cin and act_mask.cstride % 4 == 0 and act_mask.coff % 4 == 0)) and
-          w.is_contiguous() and conv_p2_ok(Cout, cin, N, H, W))
-    if p2 and os.environ.get("HRV_CONV_P2_WIDE", "1") == "0":
-        p2 = Cout % 32 == 0 and cin % 64 == 0 and not (pair is None and _thin_ok(dy, KH, KW, 1, pad, cin, N, H, W))
-    if add_after is not None:
-        ride = (p2 and add_after.C == cin and add_after.cstride % 4 == 0 and add_after.coff % 4 == 0 and add_after.t.data_ptr() % 16 == 0 and
-                add_after.coff + (cin + 3) // 4 * 4 <= add_after.cstride and os.environ.get("HRV_DGRAD_ADD_AFTER", "1") != "0")
-        if not ride:
-            out = conv_dgrad(dy, pair if pair is not None else w, H, W, stride, pad, wscale, sigma,
-                             act_mask if res_mode == 1 else None, slope, out, name, out_bf16, frozen, None, batch)
-            add_slice(add_after, out, True)
-            return out
-    if (not p2 and add is None and pair is None and stride == 1 and (Ho, Wo) == (H, W) and w.is_contiguous() and out.cstride % 4 == 0 and
-            _thin_ok(dy, KH, KW, 1, pad, cin, N, H, W)):
-        return _thin_conv(dy, w, 1, sigma, wscale, None, act_mask, res_mode, ACT_NONE, slope, out, name, fl)
-    if p2:
-        # a stride-1 data gradient is a 'same' 3x3 convolution over dY: the two-blocks-per-CU kernel
+    elif p.kernel == THIN:
+        _thin_conv(dy, w, 1, sigma, wscale, None, res, res_mode, ACT_NONE, slope, out, name, fl)
+    elif p.kernel == P2:
         pk = (conv_p2_pack(2, pair[0], pair[1], Cout, cin) if pair is not None else
               conv_p2_pack(1, w, None, Cout, cin, sigma, wscale, frozen))
-        return conv_p2(dy, pk, cin, out, mask=act_mask if res_mode == 1 else None, mask_slope=slope, name=name, flops=fl,
-                       residual=add_after, res_after_mask=add_after is not None, variant="mode 2" if pair is not None else "mode 1")
-    if stride == 1:
-        if mb and (Ho, Wo) == (H, W):   # a stride-1 data gradient is a 'same' 3x3 convolution over dY
-            cfg = ops.patch_tile(dy.bf16, KH, KW, 1, KH - 1 - pad, 1, 0, dy.Cp, cin, N, H, W) or cfg
+        conv_p2(dy, pk, cin, out, mask=act_mask, mask_slope=slope, name=name, flops=fl,
+                residual=add_after if p.ride else None, res_after_mask=p.ride, variant=p.variant)
+    elif stride == 1:
         if pair is not None:
-            packed, g, _ = pack_weight_pair_dev(pair[0], pair[1], 2, [_ceil4(cin)], [cin], cfg, 1, pad, mb, batch=batch)
+            packed, g, _ = pack_weight_pair_dev(pair[0], pair[1], 2, [_ceil4(cin)], [cin], p.cfg, 1, pad, mb, batch=batch)
         else:
-            packed, g = pack_weight_dev(w, [_ceil4(cin)], [cin], cfg, 1, 1, pad, wscale=wscale, sigma=sigma, bf16=mb,
+            packed, g = pack_weight_dev(w, [_ceil4(cin)], [cin], p.cfg, 1, 1, pad, wscale=wscale, sigma=sigma, bf16=mb,
                                         frozen=frozen, batch=batch)
-        _run_engine([(dy, 0, Cout)], packed, cin, cfg, N, Ho, Wo, H, W, g[0], g[1], 1, g[2], g[3], out,
-                    residual=act_mask, res_mode=res_mode, slope=slope, name=name, flops=fl, mma_bf16=mb)
-        return out
-    assert stride == 2, "data gradient implemented for stride 1 and 2"
-    for a in range(2):
-        for b in range(2):
-            Hp, Wp = (H - a + 1) // 2, (W - b + 1) // 2
-            if Hp <= 0 or Wp <= 0:
-                continue
-            cfg_p = _bf16_tile(cin) if mb else _f32_tile(N * Hp * Wp, cin)
+        _run_engine([(dy, 0, Cout)], packed, cin, p.cfg, N, Ho, Wo, H, W, g[0], g[1], 1, g[2], g[3], out,
+                    residual=res, res_mode=res_mode, slope=slope, name=name, flops=fl, mma_bf16=mb)
+    else:
+        for a, b, Hp, Wp, cfg_p in p.phases:
             packed, g = pack_weight_dev(w, [_ceil4(cin)], [cin], cfg_p, 2, 2, pad, (a, b), wscale, sigma, bf16=mb, batch=batch)
             _run_engine([(dy, 0, Cout)], packed, cin, cfg_p, N, Ho, Wo, Hp, Wp, g[0], g[1], 1, g[2], g[3], out,
-                        residual=act_mask, res_mode=res_mode, slope=slope, free_extent=1, out_step=2, out_off=(a, b),
+                        residual=res, res_mode=res_mode, slope=slope, free_extent=1, out_step=2, out_off=(a, b),
                         out_hw=(H, W), name=f"{name}[phase {a}{b}]", flops=fl / 4, mma_bf16=mb)
+    if add_after is not None and not p.ride:
+        add_slice(add_after, out, True)
     return out
 
 
@@ -730,69 +611,33 @@ def conv_wgrad(dy: Act, x: Act, x_up: int, ci_base: int, cin_tot: int, KH: int, 
     N, Ho, Wo, Cout = dy.N, dy.H, dy.W, dy.C
     H, W = (x.H << x_up, x.W << x_up) if x_up >= 0 else (x.H >> -x_up, x.W >> -x_up)
     assert dw.is_contiguous() and tuple(dw.shape) == (Cout, cin_tot, KH, KW), (dw.shape, Cout, cin_tot, KH, KW)
-    if (Cout == 1 and x_up == 0 and ci_base == 0 and cin_tot == x.C and not dy.bf16 and
-            (Ho, Wo) == (H + 2 * pad - KH + 1, W + 2 * pad - KW + 1) and _cout1_ok(dw, x, stride, pad, "wgrad")):
+    p = plan_wgrad(dy, x, x_up, ci_base, cin_tot, KH, KW, stride, pad, dw)
+    fl = 2.0 * N * Ho * Wo * Cout * x.C * KH * KW
+    acc = (dw.data_ptr(), 1 if accumulate else 0, None if dbias is None else dbias.data_ptr(), 1 if dbias_accumulate else 0)
+    if p.kernel == COUT1:
         S = lib.hrv_conv_cout1_wgrad_slabs(N, Ho, Wo)
         ws = _workspace(dy.t.device, 4 * S * (x.C * KH * KW + 1))
         d = _cout1_desc(dw, x, pad, 1.0, None, dy)
         d.workspace = ws.data_ptr()
-        with _Timed("wgrad", name, 2.0 * N * Ho * Wo * x.C * KH * KW, ops.act_bytes(x) + 4.0 * N * Ho * Wo, "cout1_kernel"):
-            _lib.check(lib.hrv_conv_cout1_wgrad_f32(C.byref(d), dw.data_ptr(), 1 if accumulate else 0,
-                                                    None if dbias is None else dbias.data_ptr(), 1 if dbias_accumulate else 0,
-                                                    _stream()), f"hrv_conv_cout1_wgrad_f32[{name}]")
+        with _Timed("wgrad", name, fl, ops.act_bytes(x) + 4.0 * N * Ho * Wo, COUT1):
+            _lib.check(lib.hrv_conv_cout1_wgrad_f32(C.byref(d), *acc, _stream()), f"hrv_conv_cout1_wgrad_f32[{name}]")
         return
-    wo_real = Wo
-    # The LDS-DMA kernels for bf16-stored operands take any width; the quad-staged kernel behind them needs Wo % 4 == 0.  Which one
-    # will run is the C launch path's own decision (hrv_conv2d_wgrad_{tr,s2}_supported answer from the code that launches: switches,
-    # pixel, width and slab-extent limits included), asked here with the conditions wgrad_impl (csrc/conv_bwd.hip) puts in front of
-    # each try: edit both places together.
-    served = ""
-    if MMA_BF16[0] and dy.bf16 and x.bf16 and x_up == 0:
-        if stride == 1 and (Ho, Wo) == (H, W):
-            c = lib.hrv_conv2d_wgrad_tr_supported(Cout, x.Cp, x.cstride, x.coff, dy.cstride, dy.coff, N, H, W, KH, KW, pad)
-            if c > 0:
-                served = f"conv_wgrad_tr_kernel[class {c - 1}]"
-        elif (KH, KW, stride, pad) == (4, 4, 2, 2) and (Ho, Wo) == (H // 2 + 1, W // 2 + 1):
-            c = lib.hrv_conv2d_wgrad_s2_supported(Cout, x.Cp, x.cstride, x.coff, dy.cstride, dy.coff, N, H, W)
-            if c > 0:
-                served = "conv_wgrad_s2_kernel"
-    if MMA_BF16[0] and Wo % 4 != 0 and dy.bf16 and x.bf16 and dy.coff == 0 and dy.cstride == dy.C and dy.C % 8 == 0 and not served:
-        dy = pad_width_bf16(dy)          # (the same zero columns for a bf16-stored dY: the PatchGAN with bf16 feature maps)
-        Wo = dy.W
-    if (MMA_BF16[0] and Wo % 4 != 0 and Wo >= 32 and not (x.bf16 or dy.bf16) and dy.coff == 0 and dy.cstride == dy.Cp):
-        # odd-sized maps (the PatchGAN's 513 / 257 / 129 columns): the bf16 matrix-core kernel stages quads of 4 pixels
-        # of one image row, so dY gets zero columns up to the next multiple of 4 -- they add nothing to dW or the bias
-        # gradient (the X taps they would pair with are never weighted) -- instead of taking the fp32 kernel (60-100 TFLOP/s)
+    if p.pad == "bf16":
+        dy = pad_width_bf16(dy)
+    elif p.pad == "f32":
         with _Timed("layout", "pad_width", 0.0, 2.0 * ops.act_bytes(dy)):
             dy = Act(torch.nn.functional.pad(dy.t, (0, 0, 0, (-Wo) % 4)), dy.C)
-        Wo = dy.W
+    Wo = dy.W
     need = lib.hrv_conv2d_wgrad_workspace_bytes(Cout, cin_tot, KH, KW, N * Ho * Wo)
     ws = _workspace(dy.t.device, need)
-    fl = 2.0 * N * Ho * wo_real * Cout * x.C * KH * KW
-    # mixed precision: bf16 matrix cores (needs Wo % 4 == 0: narrow odd-sized maps keep the fp32 kernel)
-    fn = lib.hrv_conv2d_wgrad_bf16mma_nhwc_f32 if (MMA_BF16[0] and Wo % 4 == 0) else lib.hrv_conv2d_wgrad_nhwc_f32
     args = (dy.t.data_ptr(), dy.cstride, dy.coff, Cout, x.t.data_ptr(), x.Cp, x.cstride, x.coff, x_up, x.C, ci_base,
-            cin_tot, N, H, W, Ho, Wo, KH, KW, stride, pad, ws.data_ptr(), ws.numel() * 4, dw.data_ptr(),
-            1 if accumulate else 0, None if dbias is None else dbias.data_ptr(), 1 if dbias_accumulate else 0)
+            cin_tot, N, H, W, Ho, Wo, KH, KW, stride, pad, ws.data_ptr(), ws.numel() * 4, *acc)
+    if p.entry == "hrv_conv2d_wgrad_bf16mma_st_nhwc_f32":       # (storage flags: bit 0 a bf16 dY, bit 1 a bf16 X)
+        args += ((1 if dy.bf16 else 0) | 2,)
     nbytes = ops.act_bytes(dy) + ops.act_bytes(x) + 4.0 * Cout * x.C * KH * KW
-    # the device kernel that serves the launch (what a rocprofv3 kernel trace groups by): the LDS-DMA kernels where C takes them, else
-    # the generic kernel by its arithmetic and storage types
-    if served:
-        kern, _, var = served.partition("[")
-        var = var.rstrip("]")
-    elif x.bf16 or dy.bf16:
-        kern, var = "conv_wgrad_kernel", "bf16 stored" if dy.bf16 else "bf16 x-stored"
-    else:
-        kern, var = "conv_wgrad_kernel", "bf16" if fn is lib.hrv_conv2d_wgrad_bf16mma_nhwc_f32 else "fp32"
-    with _Timed("wgrad", name, fl, nbytes, kern, var):
-        if x.bf16 or dy.bf16:
-            assert MMA_BF16[0] and (Wo % 4 == 0 or served), f"{name}: bf16-stored operands need the bf16 matrix-core weight gradient"
-            assert x.bf16, f"{name}: bf16 dY with an fp32 X is not built"
-            _lib.check(lib.hrv_conv2d_wgrad_bf16mma_st_nhwc_f32(*args, (1 if dy.bf16 else 0) | 2, _stream()),
-                       "hrv_conv2d_wgrad_bf16mma_st_nhwc_f32")
-        else:
-            _lib.check(fn(*args, _stream()), "hrv_conv2d_wgrad_bf16mma_nhwc_f32" if fn is lib.hrv_conv2d_wgrad_bf16mma_nhwc_f32
-                       else "hrv_conv2d_wgrad_nhwc_f32")
+    # (the record names the device kernel that serves the launch -- what a rocprofv3 kernel trace groups by)
+    with _Timed("wgrad", name, fl, nbytes, p.kernel, p.variant):
+        _lib.check(getattr(lib, p.entry)(*args, _stream()), p.entry)
 
 
 def colsum(a: Act, out: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
@@ -1486,13 +1331,6 @@ def spade_fused_forward(seg: Act, seg_shift: int, x: Act, mean: torch.Tensor, rs
 # 3x3 'same' convolution over one bf16 source, two blocks per CU (csrc/conv_p2.hip): VGG19 forward / data gradient, the
 # data gradient of the SPADE (conv_gamma, conv_beta) pair
 # ---------------------------------------------------------------------------------------------------------------
-def conv_p2_ok(K: int, cols: int, N: int, H: int, W: int) -> bool:
-    """hrv_conv_p2_supported (HRV_CONV_P2=0 switches the kernel off for A/B runs)."""
-    if os.environ.get("HRV_CONV_P2", "1") == "0":
-        return False
-    return bool(_lib.load().hrv_conv_p2_supported(K, cols, N, H, W))
-
-
 def conv_p2_pack(mode: int, w: torch.Tensor, w2: Optional[torch.Tensor], K: int, cols: int, sigma: Optional[torch.Tensor] = None,
                  wscale: float = 1.0, frozen=None) -> torch.Tensor:
     """The bf16 fragment-order weight stream of hrv_conv_p2_bf16 (mode 0 forward / 1 data gradient / 2 data gradient of a pair);

@@ -1,5 +1,6 @@
 """Case table, float64 reference and error limit of the convolution-dispatcher sweep (tests/test_gpu_conv_dispatch.py runs the
-cases on the GPU, tests/test_conv_dispatch_cases_cpu.py pins the limit to the reference and checks the table).  Plain module: no GPU.
+cases on the GPU, tests/test_conv_dispatch_cases_cpu.py pins the limit to the reference and checks the table,
+tests/test_conv_dispatch_plan_cpu.py asks hr_viton_amd/conv_dispatch.py for every case's kernel without a GPU).  Plain module: no GPU.
 
 The three entry points of hr_viton_amd/train_ops.py -- conv_forward_dev, conv_dgrad, conv_wgrad -- choose among about ten kernel
 families by predicates that live half in Python and half in the C host code.  The table walks a shape across each predicate: one case
@@ -39,7 +40,8 @@ SRC_POISON = 3.0e3          # finite junk around a SOURCE slice (a kernel may mu
 Case = namedtuple("Case", "id entry gate side mode family p env")
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# Gates walked (each has >= 1 inside and >= 1 outside case below; the file and line of every gate: DESIGN.md, section 7g)
+# Gates walked (each has >= 1 inside and >= 1 outside case below; a gate's predicate: the function of hr_viton_amd/conv_dispatch.py
+# whose docstring names the id)
 # ---------------------------------------------------------------------------------------------------------------------------------
 GATES = (
     # conv_forward_dev / _cout1_ok
@@ -543,6 +545,81 @@ def output_is_bf16(c):
     if p["out"] is not None:
         return bool(p["out"][2])
     return bool(p["out_bf16"])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the case's operands as the entry point takes them (the GPU sweep launches with them; the CPU plan test asks conv_dispatch.plan_*)
+# ---------------------------------------------------------------------------------------------------------------------------------
+def act(nchw, bf16, layout=None, poison=SRC_POISON, device="cuda"):
+    """NCHW fp32 CPU tensor -> NHWC Act on ``device``; ``layout`` = (cstride, coff): a channel slice of a wider tensor with ``poison``
+    around it (the slice's own pad channels, up to its 16-byte group, are zero).  On the ``meta`` device only shape, storage type and
+    slice layout exist."""
+    from hr_viton_amd import ops
+    N, C_, H, W = nchw.shape
+    cp = ops._cpad(C_, bf16)
+    cs, co = layout if layout else (cp, 0)
+    dt = torch.bfloat16 if bf16 else torch.float32
+    if device == "meta":
+        return ops.Act(torch.empty((N, H, W, cs), dtype=dt, device="meta"), C_, co)
+    t = torch.full((N, H, W, cs), poison, dtype=torch.float32)
+    t[..., co:co + cp] = 0
+    t[..., co:co + C_] = nchw.permute(0, 2, 3, 1)
+    return ops.Act(t.to(dt).to(device), C_, co)
+
+
+def _out_act(p, H, W, C_, device):
+    """the caller's output slice of a case (poison all over), or None where the entry point allocates"""
+    from hr_viton_amd import ops
+    if p["out"] is None:
+        return None
+    cs, co, obf = p["out"]
+    return ops.Act(torch.full((p["N"], H, W, cs), POISON, dtype=torch.bfloat16 if obf else torch.float32, device=device), C_, co)
+
+
+def entry_kwargs(c, d, device="cuda"):
+    """keyword arguments of the case's entry point (train_ops.conv_forward_dev / conv_dgrad / conv_wgrad) over the operands ``d`` of
+    make_inputs"""
+    p, st = c.p, c.mode == "st"
+    if c.entry == "fwd":
+        H, W = p["H"] << p["srcs"][0][1], p["W"] << p["srcs"][0][1]
+        Ho, Wo = (H + 2 * p["pad"] - p["K"]) // p["stride"] + 1, (W + 2 * p["pad"] - p["K"]) // p["stride"] + 1
+        return dict(w=d["w"].to(device),
+                    srcs=[(act(x, st, p["src"] if i == 0 else None, device=device), up) for i, (x, (_, up)) in enumerate(zip(d["xs"], p["srcs"]))],
+                    stride=p["stride"], pad=p["pad"], shift=None if d["shift"] is None else d["shift"].to(device),
+                    residual=None if d["res"] is None else act(d["res"], p["res"] == "bf16", device=device), act=p["act"], slope=SLOPE,
+                    out=_out_act(p, Ho << p["out_up"], Wo << p["out_up"], p["Cout"], device), out_up=p["out_up"], name=c.id, out_bf16=p["out_bf16"])
+    if c.entry == "dgrad":
+        return dict(dy=act(d["dy"], st, p["dy"], device=device), w=tuple(t.to(device) for t in d["w"]) if p["pair"] else d["w"].to(device),
+                    H=p["H"], W=p["W"], stride=p["stride"], pad=p["pad"],
+                    act_mask=None if d["mask"] is None else act(d["mask"], p["mask"] == "bf16", device=device), slope=SLOPE,
+                    out=_out_act(p, p["H"], p["W"], p["cin"], device), name=c.id, out_bf16=p["out_bf16"],
+                    add=None if d["add"] is None else act(d["add"], False, device=device),
+                    add_after=None if d["add_after"] is None else act(d["add_after"], False, device=device))
+    return dict(dy=act(d["dy"], st and p["dy"] != "f32", p["dyl"], device=device), x=act(d["x"], st, p["x"], device=device), x_up=p["x_up"],
+                ci_base=p["ci_base"], cin_tot=p["cin_tot"] or p["C"], KH=p["K"], KW=p["K"], stride=p["stride"], pad=p["pad"],
+                dw=d["dw0"].clone().to(device), accumulate=p["accumulate"], name=c.id, dbias=d["db0"].clone().to(device) if p["dbias"] else None,
+                dbias_accumulate=p["dbias_accumulate"])
+
+
+_PLAN = {"fwd": ("plan_forward", ("w", "srcs", "stride", "pad", "residual", "act", "out", "out_up", "out_bf16")),
+         "dgrad": ("plan_dgrad", ("dy", "w", "H", "W", "stride", "pad", "act_mask", "out", "out_bf16", "add", "add_after")),
+         "wgrad": ("plan_wgrad", ("dy", "x", "x_up", "ci_base", "cin_tot", "KH", "KW", "stride", "pad", "dw"))}
+
+
+def plan(c, kw, mb=None):
+    """conv_dispatch's plan for the entry point's arguments ``kw`` (``mb``: the engine mode; None = train_ops.MMA_BF16[0])"""
+    from hr_viton_amd import conv_dispatch
+    fn, keys = _PLAN[c.entry]
+    return getattr(conv_dispatch, fn)(**{k: kw[k] for k in keys}, mb=mb)
+
+
+def planned_launches(c, pl, kw):
+    """what the plan says about the launches LAUNCHES counts: {(kind, name): count}"""
+    if c.entry == "dgrad":
+        return {("ew", "add_slice"): int(kw["add_after"] is not None and not pl.ride), ("conv", ""): len(pl.phases) or 1}
+    if c.entry == "wgrad":
+        return {("layout", "pad_width"): int(pl.pad != "")}
+    return {("conv", ""): 1}
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

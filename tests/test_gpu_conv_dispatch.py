@@ -1,7 +1,7 @@
 """The convolution dispatchers on both sides of every kernel gate: every case of tests/conv_dispatch_cases.py through its public
 entry point (train_ops.conv_forward_dev / conv_dgrad / conv_wgrad), checked for the kernel family that served it, a per-element error
-against the float64 reference within the reference-derived limit, untouched poison around output slices, zero pad channels and
-accumulation exactly once.  One table of all cases goes to test_diagnostics/conv_dispatch.txt in any event."""
+against the float64 reference within the reference-derived limit, the family conv_dispatch planned before the call, untouched poison
+around output slices, zero pad channels and accumulation exactly once.  One table of all cases goes to test_diagnostics/conv_dispatch.txt in any event."""
 import os
 
 import pytest
@@ -29,19 +29,6 @@ def _table():
         f.write("families expected and never served: " + (", ".join(sorted(set(T.FAMILIES) - set(served))) or "none") + "\n")
 
 
-def _act(nchw, bf16, layout=None, poison=T.SRC_POISON):
-    """NCHW fp32 CPU tensor -> NHWC Act on the GPU; ``layout`` = (cstride, coff): a channel slice of a wider tensor with ``poison``
-    around it (the slice's own pad channels, up to its 16-byte group, are zero)"""
-    from hr_viton_amd import ops
-    N, C_, H, W = nchw.shape
-    cp = ops._cpad(C_, bf16)
-    cs, co = layout if layout else (cp, 0)
-    t = torch.full((N, H, W, cs), poison, dtype=torch.float32)
-    t[..., co:co + cp] = 0
-    t[..., co:co + C_] = nchw.permute(0, 2, 3, 1)
-    return ops.Act(t.to(torch.bfloat16 if bf16 else torch.float32).cuda(), C_, co)
-
-
 def _nchw(a):
     return a.t[..., a.coff:a.coff + a.C].float().cpu().permute(0, 3, 1, 2).contiguous()
 
@@ -55,49 +42,6 @@ def _check_surroundings(a, what, pad_zero=True):
     assert outside.numel() == 0 or bool((outside == T.POISON).all()), f"{what}: the tensor around the output slice was written"
     if pad_zero and cp > a.C:
         assert bool((t[..., a.coff + a.C:a.coff + cp] == 0).all()), f"{what}: pad channels are not zero"
-
-
-def _run_fwd(c, d, tops, ops):
-    p, st = c.p, c.mode == "st"
-    srcs = [(_act(x, st, p["src"] if i == 0 else None), up) for i, (x, (_, up)) in enumerate(zip(d["xs"], p["srcs"]))]
-    w = d["w"].cuda()
-    shift = None if d["shift"] is None else d["shift"].cuda()
-    res = None if d["res"] is None else _act(d["res"], p["res"] == "bf16")
-    out = None
-    if p["out"] is not None:
-        cs, co, obf = p["out"]
-        Ho, Wo = d["ref"].shape[2], d["ref"].shape[3]
-        out = ops.Act(torch.full((p["N"], Ho, Wo, cs), T.POISON, dtype=torch.bfloat16 if obf else torch.float32, device="cuda"), p["Cout"], co)
-    got = tops.conv_forward_dev(w, srcs, p["stride"], p["pad"], shift=shift, residual=res, act=p["act"], slope=T.SLOPE, out=out,
-                                out_up=p["out_up"], name=c.id, out_bf16=p["out_bf16"])
-    return got, out is not None
-
-
-def _run_dgrad(c, d, tops, ops):
-    p, st = c.p, c.mode == "st"
-    dy = _act(d["dy"], st, p["dy"])
-    w = tuple(t.cuda() for t in d["w"]) if p["pair"] else d["w"].cuda()
-    mask = None if d["mask"] is None else _act(d["mask"], p["mask"] == "bf16")
-    add = None if d["add"] is None else _act(d["add"], False)
-    add_after = None if d["add_after"] is None else _act(d["add_after"], False)
-    out = None
-    if p["out"] is not None:
-        cs, co, obf = p["out"]
-        out = ops.Act(torch.full((p["N"], p["H"], p["W"], cs), T.POISON, dtype=torch.bfloat16 if obf else torch.float32, device="cuda"), p["cin"], co)
-    got = tops.conv_dgrad(dy, w, p["H"], p["W"], p["stride"], p["pad"], act_mask=mask, slope=T.SLOPE, out=out, name=c.id,
-                          out_bf16=p["out_bf16"], add=add, add_after=add_after)
-    return got, out is not None
-
-
-def _run_wgrad(c, d, tops, ops):
-    p, st = c.p, c.mode == "st"
-    x = _act(d["x"], st, p["x"])
-    dy = _act(d["dy"], st and p["dy"] != "f32", p["dyl"])
-    dw = d["dw0"].clone().cuda()
-    db = d["db0"].clone().cuda() if p["dbias"] else None
-    tops.conv_wgrad(dy, x, p["x_up"], p["ci_base"], p["cin_tot"] or p["C"], p["K"], p["K"], p["stride"], p["pad"], dw,
-                    accumulate=p["accumulate"], name=c.id, dbias=db, dbias_accumulate=p["dbias_accumulate"])
-    return dw, db
 
 
 def _coords(shape, i):
@@ -125,7 +69,10 @@ def test_conv_dispatch(cid, monkeypatch):
     ops.profile_begin()
     try:
         try:
-            res = {"fwd": _run_fwd, "dgrad": _run_dgrad, "wgrad": _run_wgrad}[c.entry](c, d, tops, ops)
+            kw = T.entry_kwargs(c, d)
+            plan = T.plan(c, kw)                # (before the call: plan and launch cannot drift apart)
+            got = {"fwd": tops.conv_forward_dev, "dgrad": tops.conv_dgrad, "wgrad": tops.conv_wgrad}[c.entry](**kw)
+            res = (kw["dw"], kw["dbias"]) if c.entry == "wgrad" else (got, kw["out"] is not None)
         finally:
             recs = ops.profile_end(kernels=True, variants=True)
             tops.MMA_BF16[0] = prev
@@ -177,6 +124,7 @@ def test_conv_dispatch(cid, monkeypatch):
     _ROWS[cid] = head + " | %-36s %9.2f %9.3f  %s" % (served, worst[0], worst[1], worst[2])
     print("\n" + _ROWS[cid])
     assert served == c.family, f"{cid}: served by {served}, the table expects {c.family}"           # 2.
+    assert plan.family == served, f"{cid}: conv_dispatch planned {plan.family}, the profile record reports {served}"
     for kind, name, count in T.LAUNCHES.get(cid, ()):       # (the side of a gate whose two sides share a family)
         n = sum(1 for r in recs if r[0] == kind and name in r[1])
         assert n == count, f"{cid}: {n} launches of kind {kind!r} {name!r}, the table expects {count}: {[(r[0], r[1]) for r in recs]}"
