@@ -1,14 +1,20 @@
 #!/usr/bin/env python3
 """Drop-in for the reference's ``evaluate.py`` (same flags, same pairing, same output files): SSIM, MSE and LPIPS of a folder
-of try-on outputs against the ground-truth photos, computed on the MI355X-native kernels (csrc/metrics.hip + the fp32 conv
-engine for LPIPS's AlexNet).
+of try-on outputs against the ground-truth photos and the Inception Score of the outputs, computed on the MI355X-native kernels
+(csrc/metrics.hip, csrc/inception.hip + the fp32 conv engine for LPIPS's AlexNet and the score's Inception-v3).
 
 Decoding and resizing stay on the CPU in DataLoader workers (data loading, like cp_dataset); the metrics run on the GPU in
 batches.  Differences from the reference script:
   * LPIPS weights are read from files, never downloaded: ``--lpips_weights`` (the v0.1 ``alex.pth``, default the reference's
     location) and ``--alexnet_weights`` (torchvision's AlexNet state dict, default torch's hub-cache file).  Missing weights
     stop the run unless ``--lpips_random_init`` is given (plumbing only; the output says so).
-  * the Inception Score needs a pretrained Inception-v3: it is not computed and is written as nan.
+  * the Inception Score needs torchvision's pretrained Inception-v3 state dict, read from a file and never downloaded:
+    ``--inception_weights`` (default: torch's hub-cache file).  Without the file the score is not computed and is written as nan;
+    ``--inception_random_init`` computes it on seeded random weights instead (plumbing only; the output says so).
+    ``--is_splits`` is the reference's constant ``splits = 1``.
+  * the reference sizes its array of Inception predictions by the number of ground-truth files, so a ground-truth folder with
+    more files than predictions leaves zero rows and its score is nan.  Here the predictions there are get scored, and a note is
+    printed when the two counts differ.
   * MSE is written as a plain float (the reference's f-string prints the CUDA tensor).
   * non-image files in --predict_dir (e.g. the lpips.txt / eval.txt of an earlier run) are skipped.
 The reference's quirk of dividing the three averages by the number of ground-truth files is kept, so the numbers stay
@@ -29,10 +35,17 @@ if ROOT not in sys.path:
 
 IMAGE_EXT = (".jpg", ".jpeg", ".png", ".bmp", ".webp", ".tif", ".tiff")
 ALEXNET_FILE = "alexnet-owt-7be5be79.pth"
+INCEPTION_FILES = ("inception_v3_google-0cc3c7bd.pth", "inception_v3_google-1a9a5a14.pth")    # torchvision's, newer release first
 
 
 def _default_alexnet_weights():
     return os.path.join(torch.hub.get_dir(), "checkpoints", ALEXNET_FILE)
+
+
+def _default_inception_weights():
+    """The first of torchvision's two file names that exists in torch's hub cache (else the first name, which then does not exist)."""
+    paths = [os.path.join(torch.hub.get_dir(), "checkpoints", f) for f in INCEPTION_FILES]
+    return next((p for p in paths if os.path.isfile(p)), paths[0])
 
 
 def get_opt(argv=None):
@@ -46,12 +59,23 @@ def get_opt(argv=None):
                    help="torchvision alexnet state dict (default: torch's hub cache, %s; read only if present)" % ALEXNET_FILE)
     p.add_argument("--lpips_random_init", action="store_true",
                    help="plumbing only: LPIPS on randomly initialised AlexNet / lin weights (the output is labelled)")
-    p.add_argument("--seed", type=int, default=0, help="torch seed of the random initialisation (--lpips_random_init)")
+    p.add_argument("--inception_weights", default=None,
+                   help="torchvision inception_v3 state dict for the Inception Score (default: torch's hub cache, %s; without the "
+                        "file the score is written as nan)" % " or ".join(INCEPTION_FILES))
+    p.add_argument("--inception_random_init", action="store_true",
+                   help="plumbing only: the Inception Score on a randomly initialised Inception-v3 (the output is labelled)")
+    p.add_argument("--is_splits", type=int, default=1, help="splits of the Inception Score (the reference's constant 1)")
+    p.add_argument("--seed", type=int, default=0,
+                   help="torch seed of the random initialisations (--lpips_random_init, --inception_random_init)")
     p.add_argument("-j", "--workers", type=int, default=4)
     p.add_argument("-b", "--batch-size", type=int, default=16)
     opt = p.parse_args(argv)
     if opt.alexnet_weights is None:
         opt.alexnet_weights = _default_alexnet_weights()
+    if opt.inception_weights is None:
+        opt.inception_weights = _default_inception_weights()
+    if opt.is_splits < 1:
+        p.error("--is_splits must be at least 1")
     return opt
 
 
@@ -69,10 +93,11 @@ def _rgb(img: Image.Image) -> np.ndarray:
 
 
 class PairDataset(torch.utils.data.Dataset):
-    """One prediction and its ground truth as decoded: full-size RGB uint8 (SSIM / MSE) and the 128x128 resizes (LPIPS)."""
+    """One prediction and its ground truth as decoded: full-size RGB uint8 (SSIM / MSE), the 128x128 resizes (LPIPS) and, with
+    ``with_is``, the prediction's 299x299 resize (Inception Score)."""
 
-    def __init__(self, opt, pred_list):
-        self.opt, self.pred_list = opt, pred_list
+    def __init__(self, opt, pred_list, with_is=False):
+        self.opt, self.pred_list, self.with_is = opt, pred_list, with_is
 
     def __len__(self):
         return len(self.pred_list)
@@ -89,9 +114,12 @@ class PairDataset(torch.utils.data.Dataset):
                 raise NotImplementedError(opt.resolution)
         pred_img = Image.open(os.path.join(opt.predict_dir, name))
         assert gt_img.size == pred_img.size, f"{gt_img.size} vs {pred_img.size}"
-        return {"name": name, "gt": _rgb(gt_img), "pred": _rgb(pred_img),
+        item = {"name": name, "gt": _rgb(gt_img), "pred": _rgb(pred_img),
                 "gt128": _rgb(gt_img.resize((128, 128), Image.BILINEAR)),        # Transforms.Resize((128, 128)) on a PIL image
                 "pred128": _rgb(pred_img.resize((128, 128), Image.BILINEAR))}
+        if self.with_is:
+            item["pred299"] = _rgb(pred_img.resize((299, 299), Image.BILINEAR))  # Transforms.Resize((299, 299)), evaluate.py:34
+        return item
 
 
 def load_lpips(opt):
@@ -113,6 +141,58 @@ def load_lpips(opt):
               "the paper's metric", file=sys.stderr, flush=True)
     model.eval()
     return model, not have
+
+
+def load_inception(opt):
+    """(Inception3 or None, random_init): torchvision's inception_v3 from ``--inception_weights``; seeded random weights with
+    ``--inception_random_init`` when the file is missing; None when there is neither (the score is then written as nan)."""
+    have = os.path.isfile(opt.inception_weights)
+    if not have and not opt.inception_random_init:
+        return None, False
+    import hr_viton_amd  # noqa: F401
+    from hr_viton_amd.inception import Inception3
+    torch.manual_seed(opt.seed)
+    model = Inception3(transform_input=False)
+    if have:
+        model.load_state_dict(torch.load(opt.inception_weights, map_location="cpu"))
+    else:
+        print("WARNING: the Inception Score runs on a RANDOMLY initialised Inception-v3 (--inception_random_init): it is not "
+              "the paper's metric", file=sys.stderr, flush=True)
+    model.eval()
+    return model, not have
+
+
+class InceptionScorer:
+    """softmax(inception_v3(pred299)) of a loader batch as float64 rows [n, 1000] on the host (evaluate.py:76)."""
+
+    def __init__(self, model):
+        self.model = model
+        self.dev = torch.device("cuda")
+
+    def __call__(self, batch):
+        x = torch.from_numpy(np.stack([it["pred299"] for it in batch])).pin_memory().to(self.dev, non_blocking=True)
+        return self.model.forward_u8(x).cpu().numpy().astype(np.float64)
+
+
+def inception_score(preds, splits=1):
+    """evaluate.py:97-106 in float64: per split ``exp(mean_i KL(p_i || p_mean))`` with ``scipy.stats.entropy(pk, qk)``'s
+    normalisation of both arguments (terms with p == 0 contribute 0); returns (mean, std) over the splits."""
+    preds = np.asarray(preds, dtype=np.float64)
+    n = (preds.shape[0] if preds.ndim == 2 else 0) // splits
+    if n < 1:
+        return float("nan"), float("nan")
+    split_scores = []
+    for k in range(splits):
+        part = preds[k * n:(k + 1) * n, :]
+        py = np.mean(part, axis=0)
+        q = py / py.sum()
+        scores = []
+        for i in range(part.shape[0]):
+            p = part[i, :] / part[i, :].sum()
+            nz = p > 0
+            scores.append(float(np.sum(p[nz] * np.log(p[nz] / q[nz]))))
+        split_scores.append(np.exp(np.mean(scores)))
+    return float(np.mean(split_scores)), float(np.std(split_scores))
 
 
 class GpuScorer:
@@ -145,7 +225,8 @@ class GpuScorer:
         return list(zip(ssim, mse, [float(v) for v in lp.cpu().tolist()]))
 
 
-def write_results(predict_dir, lpips_list, avg_ssim, avg_mse, avg_distance, is_mean, is_std, random_init=False):
+def write_results(predict_dir, lpips_list, avg_ssim, avg_mse, avg_distance, is_mean, is_std, random_init=False,
+                  inception_random_init=False):
     lpips_list = sorted(lpips_list, key=lambda x: x[1], reverse=True)
     with open(os.path.join(predict_dir, "lpips.txt"), "a") as f:
         for name, score in lpips_list:
@@ -155,12 +236,17 @@ def write_results(predict_dir, lpips_list, avg_ssim, avg_mse, avg_distance, is_m
         f.write(f"IS_mean : {is_mean} / IS_std : {is_std}\n")
         if random_init:
             f.write("LPIPS weights : random init (plumbing only)\n")
+        if inception_random_init:
+            f.write("Inception weights : random init (plumbing only)\n")
 
 
-def evaluation(opt, pred_list, gt_list, scorer):
-    """evaluate.py:28-114 minus the Inception Score.  Returns (avg_ssim, avg_mse, avg_distance, lpips_list, timings)."""
-    loader = torch.utils.data.DataLoader(PairDataset(opt, pred_list), batch_size=max(1, opt.batch_size), shuffle=False,
-                                         num_workers=opt.workers, collate_fn=list)
+def evaluation(opt, pred_list, gt_list, scorer, is_scorer=None):
+    """evaluate.py:28-114 up to the score itself.  Returns (avg_ssim, avg_mse, avg_distance, lpips_list, timings); with an
+    ``is_scorer`` the Inception predictions of all pairs, float64 [pairs, 1000] in loader order, are ``timings["inception_preds"]``
+    (main() takes them out again) and the time spent on them ``timings["inception_s"]``."""
+    loader = torch.utils.data.DataLoader(PairDataset(opt, pred_list, with_is=is_scorer is not None),
+                                         batch_size=max(1, opt.batch_size), shuffle=False, num_workers=opt.workers, collate_fn=list)
+    preds, t_is = [], 0.0
     sum_ssim = sum_mse = sum_dist = 0.0
     lpips_list = []
     t_wait = t_gpu = 0.0
@@ -176,6 +262,10 @@ def evaluation(opt, pred_list, gt_list, scorer):
             break
         res = scorer(batch)
         t_gpu += time.perf_counter() - t1
+        if is_scorer is not None:
+            t2 = time.perf_counter()
+            preds.append(np.asarray(is_scorer(batch), dtype=np.float64))
+            t_is += time.perf_counter() - t2
         for item, (s, m, d) in zip(batch, res):
             step += 1
             sum_ssim += s
@@ -187,31 +277,54 @@ def evaluation(opt, pred_list, gt_list, scorer):
     if n != len(pred_list):
         print(f"note: averages are divided by the number of ground-truth files ({n}), as in the reference, not by the number "
               f"of predictions ({len(pred_list)})", file=sys.stderr)
-    return sum_ssim / n, sum_mse / n, sum_dist / n, lpips_list, {"loader_wait_s": t_wait, "gpu_s": t_gpu}
+    timings = {"loader_wait_s": t_wait, "gpu_s": t_gpu}
+    if is_scorer is not None:
+        timings["inception_s"] = t_is
+        timings["inception_preds"] = np.concatenate(preds, axis=0) if preds else np.zeros((0, 1000))
+    return sum_ssim / n, sum_mse / n, sum_dist / n, lpips_list, timings
 
 
-def main(argv=None, scorer=None):
+def main(argv=None, scorer=None, is_scorer=None):
+    """``scorer`` / ``is_scorer``: stand-ins for GpuScorer / InceptionScorer (tests).  With a ``scorer`` and no ``is_scorer`` nothing
+    is loaded and the Inception Score is nan."""
     opt = get_opt(argv)
     pred_list = list_predictions(opt.predict_dir)
     gt_list = sorted(os.listdir(opt.ground_truth_dir))
     random_init = False
+    is_random_init = is_scorer is not None and opt.inception_random_init
     if scorer is None:
         model, random_init = load_lpips(opt)
         scorer = GpuScorer(model)
+        if is_scorer is None:
+            inception, is_random_init = load_inception(opt)
+            if inception is not None:
+                is_scorer = InceptionScorer(inception)
     t0 = time.perf_counter()
     with torch.no_grad():
-        avg_ssim, avg_mse, avg_distance, lpips_list, timings = evaluation(opt, pred_list, gt_list, scorer)
+        avg_ssim, avg_mse, avg_distance, lpips_list, timings = evaluation(opt, pred_list, gt_list, scorer, is_scorer)
     timings["total_s"] = time.perf_counter() - t0
+    preds = timings.pop("inception_preds", None)
     print("Calculate Inception Score...")
-    print("Inception Score: not computed (it needs a pretrained Inception-v3, which is not available here): written as nan",
-          file=sys.stderr)
-    is_mean = is_std = float("nan")
-    write_results(opt.predict_dir, lpips_list, avg_ssim, avg_mse, avg_distance, is_mean, is_std, random_init)
+    if preds is None:
+        print("Inception Score: not computed (it needs a pretrained Inception-v3: --inception_weights, now %r, does not exist and "
+              "nothing is downloaded; --inception_random_init for plumbing runs): written as nan" % opt.inception_weights,
+              file=sys.stderr)
+        is_mean = is_std = float("nan")
+    else:
+        if len(gt_list) != len(pred_list):
+            print(f"note: the Inception Score is computed over the {len(pred_list)} predictions; the reference sizes its array by "
+                  f"the number of ground-truth files ({len(gt_list)}) and would score the zero rows that leaves as nan",
+                  file=sys.stderr)
+        is_mean, is_std = inception_score(preds, opt.is_splits)
+    write_results(opt.predict_dir, lpips_list, avg_ssim, avg_mse, avg_distance, is_mean, is_std, random_init, is_random_init)
     print("SSIM : %f / MSE : %f / LPIPS : %f" % (avg_ssim, avg_mse, avg_distance))
     print("IS_mean : %f / IS_std : %f" % (is_mean, is_std))
     if random_init:
         print("(LPIPS from randomly initialised weights: plumbing only)")
-    return {"ssim": avg_ssim, "mse": avg_mse, "lpips": avg_distance, "pairs": len(pred_list), "timings": timings}
+    if is_random_init:
+        print("(Inception Score from randomly initialised weights: plumbing only)")
+    return {"ssim": avg_ssim, "mse": avg_mse, "lpips": avg_distance, "is_mean": is_mean, "is_std": is_std, "pairs": len(pred_list),
+            "timings": timings}
 
 
 if __name__ == "__main__":

@@ -68,16 +68,17 @@ def _f32_tile(M: int, cout: int) -> int:
 
 
 def patch_tile(bf16_sources: bool, KH: int, KW: int, stride: int, pad: int, nsrc: int, up: int, C: int, cols: int,
-               N: int, H: int, W: int, wide: bool = False) -> int:
+               N: int, H: int, W: int, wide: bool = False, pad_w: Optional[int] = None) -> int:
     """Patch-mode tile of the conv engine (conv_f32.hip, VAR bit 6) for this layer, or 0.  Patch mode: 3x3 stride-1
     'same' convolution over ONE bf16-stored source with C % 128 == 0; the 8x16-pixel tile keeps its 10x18 halo
     patch resident in LDS and only the weight tiles stream (the implicit-GEMM gather re-reads every activation
     pixel from L2 once per tap).  tile_cfg 17: 128 columns, 18: 64 columns (column counts that are odd multiples
     of 64 -- the SPADE gamma|beta convs of the 80/144/272-channel blocks).  Needs enough tiles to fill the chip
     (else the gather tiles with split-K win).  HRV_CONV_PATCH=0 disables it, =16 selects the 16x16-pixel tile.
+    ``pad_w``: the horizontal padding where the caller sets one (None: ``pad``); 'same' means 1 in BOTH directions.
     Gates: fwd.patch.tiles512, fwd.patch.c64pad, fwd.patch.C%128, fwd.patch.env, dgrad.patch.tiles512."""
     env = os.environ.get("HRV_CONV_PATCH", "1")
-    if not (bf16_sources and KH == 3 and KW == 3 and stride == 1 and pad == 1 and nsrc == 1 and up == 0 and
+    if not (bf16_sources and KH == 3 and KW == 3 and stride == 1 and pad == 1 and pad_w in (None, 1) and nsrc == 1 and up == 0 and
             C % 128 == 0 and env != "0"):
         return 0
     # tile_cfg 19 (conv_patchw.hip): 16x16-pixel tiles x up to 192 columns per block, one block per CU, weights
@@ -99,7 +100,8 @@ def patch_tile(bf16_sources: bool, KH: int, KW: int, stride: int, pad: int, nsrc
 
 
 def engine_tile(engine: str, M: int, cols: int, bf16_src: bool, KH: int, KW: int, stride: int, pad: int, nsrc: int, up: int,
-                C: int, N: int, H: int, W: int, c1x1: int = 0, wide: bool = False, base: Optional[int] = None) -> int:
+                C: int, N: int, H: int, W: int, c1x1: int = 0, wide: bool = False, base: Optional[int] = None,
+                pad_w: Optional[int] = None) -> int:
     """tile_cfg of a layer on the generic engine (conv_f32.hip).  ``engine`` picks the tile a layer starts from unless the
     caller has one (``base``: the SPADE gamma|beta sites, whose column order fixes the tile width):
       "mb"    bf16 matrix cores, training (MMA_BF16) or inference over fp32 tensors: the least column padding (_bf16_tile);
@@ -111,6 +113,8 @@ def engine_tile(engine: str, M: int, cols: int, bf16_src: bool, KH: int, KW: int
     applied: data gradients, training layers with several sources) and 64-column multiples takes tile 6 -- one or two K-tiles,
     the block is all prologue and epilogue, so the small tile with 64-byte rows keeps more blocks resident (conv_shared as a 1x1
     over the 72 expanded taps: 0.39 vs 0.48 ms).  Then the LDS-resident patch tile where ``patch_tile`` has one.
+    ``pad_w``: ops.ConvLayer's horizontal padding (None: ``pad``); only the patch tile's 'same' gate reads it -- no other rule here
+    looks at the padding, and the tiles themselves take any (csrc/conv_f32.hip gathers with pad and pad_w separately).
     Gates: fwd.tile6.Cout%64, fwd.tile6.Cp<=128 (and patch_tile's)."""
     if base is not None:
         cfg = base
@@ -126,7 +130,7 @@ def engine_tile(engine: str, M: int, cols: int, bf16_src: bool, KH: int, KW: int
         return cfg
     if KH == 1 and KW == 1 and 0 < c1x1 <= 128 and cols % 64 == 0:
         cfg = 6
-    return patch_tile(True, KH, KW, stride, pad, nsrc, up, C, cols, N, H, W, wide) or cfg
+    return patch_tile(True, KH, KW, stride, pad, nsrc, up, C, cols, N, H, W, wide, pad_w) or cfg
 
 
 # ---------------------------------------------------------------------------------------------------------------

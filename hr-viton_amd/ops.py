@@ -247,7 +247,9 @@ class ConvLayer:
     def __init__(self, weight: torch.Tensor, src_real: Sequence[int], device, scale: Optional[torch.Tensor] = None,
                  shift: Optional[torch.Tensor] = None, stride: int = 1, pad: int = 1, act: int = ACT_NONE,
                  slope: float = 0.2, name: str = "conv", bf16: bool = False, out_f32: bool = False,
-                 mma_bf16: bool = False):
+                 mma_bf16: bool = False, pad_w: Optional[int] = None):
+        # pad_w: horizontal padding where it differs from the vertical ``pad`` (the 1x7 / 7x1 / 1x3 / 3x1 layers of Inception-v3);
+        # None: the same as ``pad``, and the descriptor is the one a call without it builds (pad_w_plus1 = 0)
         # bf16: sources + weights are bf16 (fp32 accumulate); out_f32: in bf16 mode the output is written
         # as fp32 (tensors that feed an InstanceNorm stay fp32)
         # mma_bf16: every tensor stays fp32, only the matrix-core operands are rounded to bf16 while staged
@@ -265,6 +267,8 @@ class ConvLayer:
         self.src_pad = [_cpad(c, bf16) for c in src_real]
         self.device = device
         self.stride, self.pad, self.act, self.slope, self.name = stride, pad, act, slope, name
+        assert pad_w is None or pad_w >= 0, (name, pad_w)
+        self.pad_w = pad_w
         self.scale = None if scale is None else scale.detach().to(device, torch.float32).contiguous()
         self.shift = None if shift is None else shift.detach().to(device, torch.float32).contiguous()
         self._packed = {}
@@ -292,7 +296,8 @@ class ConvLayer:
         return self._packed[cfg]
 
     def out_hw(self, H: int, W: int) -> Tuple[int, int]:
-        return ((H + 2 * self.pad - self.KH) // self.stride + 1, (W + 2 * self.pad - self.KW) // self.stride + 1)
+        pw = self.pad if self.pad_w is None else self.pad_w
+        return ((H + 2 * self.pad - self.KH) // self.stride + 1, (W + 2 * pw - self.KW) // self.stride + 1)
 
     def flops(self, N, Ho, Wo) -> float:
         return 2.0 * N * Ho * Wo * getattr(self, "flops_cout", self.Cout) * sum(self.src_real) * self.KH * self.KW
@@ -320,6 +325,8 @@ class ConvLayer:
         mixed = (0 if out.bf16 else 1) | (0 if (residual is None or residual.bf16) else 2)
         d.N, d.H, d.W, d.Ho, d.Wo = N, H, W, Ho, Wo
         d.KH, d.KW, d.stride, d.pad = self.KH, self.KW, self.stride, self.pad
+        if self.pad_w is not None:
+            d.pad_w_plus1 = self.pad_w + 1
         d.nsrc = len(specs)
         for i, (a, up, pre) in enumerate(specs):
             assert a.C == self.src_real[i], (self.name, i, a.C, self.src_real[i])
@@ -331,7 +338,7 @@ class ConvLayer:
         naive = os.environ.get("HRV_CONV_IMPL", "mfma") == "naive"
         if cfg is None:
             cfg = engine_tile("mb" if self.mixed else "serve", N * Ho * Wo, self.Cout, self.bf16, self.KH, self.KW, self.stride,
-                              self.pad, len(specs), up0, self.src_pad[0], N, H, W, c1x1=sum(self.src_pad))
+                              self.pad, len(specs), up0, self.src_pad[0], N, H, W, c1x1=sum(self.src_pad), pad_w=self.pad_w)
         forced = os.environ.get("HRV_CONV_TILE") if (spade is None and not self.mixed) else None
         if forced is not None:
             cfg = int(forced)

@@ -915,6 +915,20 @@ typedef struct {
  * networks_basic.py:60-86, spatial=False); ntaps <= 8, taps is a host array */
 int hrv_lpips_head_f32(const hrv_lpips_tap_t* taps, int32_t ntaps, int32_t B, float* out, hrv_stream_t stream);
 
+/* ---- Inception-v3 (evaluate.py's Inception Score; inception.hip).  The convolutions run on hrv_conv2d_nhwc_f32. ---- */
+/* The network's two 3x3 pools over channels [coff, coff + C) of NHWC fp32 tensors (C, cstride, coff multiples of 4), so a pool reads
+ * a slice and writes a slice of a concatenation.  mode 0: max, stride 2, no padding, floor -> [N,(H-3)/2+1,(W-3)/2+1,C] (exact);
+ * mode 1: average, stride 1, padding 1, always divided by 9 (F.avg_pool2d's count_include_pad=True) -> [N,H,W,C], the nine values
+ * added in double and rounded once.  Channels of `y` outside the slice are not touched.  x and y must not overlap. */
+int hrv_pool3x3_nhwc_f32(const float* x, int32_t N, int32_t H, int32_t W, int32_t C, int32_t x_cstride, int32_t x_coff, int32_t mode,
+                         float* y, int32_t y_cstride, int32_t y_coff, hrv_stream_t stream);
+/* The classifier head over the last feature map feat [N,HW,cstride] (channels [0, C)): pooled[n][c] = mean over the HW pixels
+ * (workspace, N*C floats), logits[n][k] = sum_c pooled[n][c] * fc_w[k][c] + fc_b[k] (fc_b may be NULL), and -- where probs is not
+ * NULL -- probs[n][:] = softmax(logits[n][:]).  Fixed summation orders that do not depend on N: an image's row has the same bits
+ * in every batch and on every run. */
+int hrv_inception_head_f32(const float* feat, int32_t N, int32_t HW, int32_t C, int32_t cstride, const float* fc_w, const float* fc_b,
+                           int32_t K, float* pooled, float* logits, float* probs, hrv_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

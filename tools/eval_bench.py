@@ -6,7 +6,10 @@
    of the larger of two floors -- bytes (both uint8 images read once, at the measured 6.29 TB/s copy rate) and VALU FLOPs (the
    kernel's separable-filter arithmetic at the 157.3 TFLOP/s fp32 vector peak);
 2. LPIPS (input conversion, five convolutions, two pools, fused head) per pair at 128x128, batch B;
-3. a full evaluate.py run over N synthetic 1024x768 JPEG pairs in a child process: wall time split into time blocked on the
+3. Inception-v3 (input conversion, 94 convolutions, the pools, the head) per image at 299x299, batch 1 and B, on seeded random
+   weights: event time per image, and the conv engine's TFLOP/s over the 94 convolutions from a per-launch profile (their
+   algorithmic FLOPs, 11.4 GFLOP = 5.7 G multiply-adds per image, over the sum of their event times);
+4. a full evaluate.py run over N synthetic 1024x768 JPEG pairs in a child process: wall time split into time blocked on the
    DataLoader (CPU decode / resize) and time in the GPU scorer.
 Event times include launch gaps; for kernel-only times run this under ``rocprofv3 --kernel-trace --stats`` in a run of its own.
 Prints one JSON line.
@@ -27,7 +30,9 @@ import torch  # noqa: E402
 
 import hr_viton_amd  # noqa: E402,F401
 from hr_viton_amd import metrics  # noqa: E402
+from hr_viton_amd import ops  # noqa: E402
 from hr_viton_amd.eval_models import PerceptualLoss  # noqa: E402
+from hr_viton_amd.inception import Inception3  # noqa: E402
 
 HBM_BPS = 6.29e12          # measured float4 copy rate (MI355X_MICROARCH: 79 % of the 8 TB/s spec)
 VALU_FLOPS = 157.3e12      # fp32 vector peak
@@ -54,6 +59,29 @@ def timed(fn, reps):
     e.record()
     torch.cuda.synchronize()
     return s.elapsed_time(e) / 1e3 / reps
+
+
+def inception_bench(B, reps):
+    """Per batch size: event time per image of forward_u8, and from one profiled pass the convolutions' FLOPs, their summed event
+    times and the launch count."""
+    torch.manual_seed(0)
+    net = Inception3().eval()
+    g = torch.Generator(device="cuda").manual_seed(1)
+    out = {}
+    for b in sorted({1, B}):
+        img = torch.randint(0, 256, (b, 299, 299, 3), dtype=torch.uint8, device="cuda", generator=g)
+        t = timed(lambda: net.forward_u8(img), reps)
+        net.forward_u8(img)
+        ops.profile_begin()
+        net.forward_u8(img)
+        rec = ops.profile_end()
+        conv = [r for r in rec if r[0] == "conv"]
+        flops, ms = sum(r[2] for r in conv), sum(r[4] for r in conv)
+        out[f"batch_{b}"] = {"us_per_image": 1e6 * t / b, "launches_profiled": len(rec), "convs": len(conv),
+                             "conv_gflop_per_image": flops / b / 1e9, "conv_event_ms": ms,
+                             "conv_tflops_over_event_time": flops / (ms * 1e-3) / 1e12 if ms > 0 else None,
+                             "tflops_over_wall": flops / t / 1e12}
+    return out
 
 
 def e2e(n, workers, batch):
@@ -105,7 +133,8 @@ def main():
     res = {"pair_stats": {"B": B, "H": H, "W": W, "ms_per_pair": 1e3 * t_ps / B, "floor_ms_per_pair": 1e3 * floor / B,
                           "byte_floor_ms_per_pair": 1e3 * fb / B, "valu_floor_ms_per_pair": 1e3 * ff / B,
                           "fraction_of_floor": floor / t_ps},
-           "lpips_128": {"B": B, "ms_per_pair": 1e3 * t_lp / B}}
+           "lpips_128": {"B": B, "ms_per_pair": 1e3 * t_lp / B},
+           "inception_299": inception_bench(B, a.reps)}
     if a.e2e:
         res["evaluate_py"] = e2e(a.e2e, a.workers, B)
     print(json.dumps(res))
