@@ -178,6 +178,27 @@ class PNetLin(nn.Module):
                                                    both[i * N:].data_ptr(), _stream()), "hrv_lpips_prep_nchw_f32")
         return self.distance_prepped(Act(both, 3)).view(N, 1, 1, 1)
 
+    def forward_resized(self, in0: torch.Tensor, in1: torch.Tensor, size=(128, 128), normalize: bool = False) -> torch.Tensor:
+        """``forward(T2(in0), T2(in1))`` with ``T2 = transforms.Resize(size)`` applied to fp32 NCHW tensors, the LPIPS call of
+        train_generator.py:482,578 -> [N,1,1,1].  The resize is bilinear, align_corners=False, WITHOUT antialiasing: that is what
+        the reference's pinned environment (pytorch-lts 1.8, torchvision 0.9) does to tensor inputs; current torchvision
+        antialiases them by default, and we follow the former.  Resize and ScalingLayer of both images are one launch
+        (csrc/validate.hip), bit-identical to ``forward(glue.resize_nchw(in0, size), glue.resize_nchw(in1, size))``."""
+        for t in (in0, in1):
+            ops.require_cuda(t, "LPIPS")
+            if t.dtype != torch.float32 or t.dim() != 4 or t.shape[1] != 3:
+                raise HrvError("LPIPS: expected fp32 images [N,3,H,W]")
+        assert in0.shape == in1.shape, (in0.shape, in1.shape)
+        N, _, H, W = in0.shape
+        Ho, Wo = int(size[0]), int(size[1])
+        both = torch.empty((2 * N, Ho, Wo, 4), dtype=torch.float32, device=in0.device)
+        _, _, (sh, sc) = self.plan(in0.device)
+        lib = _lib.load()
+        _lib.check(lib.hrv_lpips_prep_resize_nchw_f32(in0.detach().contiguous().data_ptr(), in1.detach().contiguous().data_ptr(),
+                                                      N, H, W, Ho, Wo, int(bool(normalize)), sh, sc, both.data_ptr(), _stream()),
+                   "hrv_lpips_prep_resize_nchw_f32")
+        return self.distance_prepped(Act(both, 3)).view(N, 1, 1, 1)
+
 
 def maxpool3x3s2(a: Act) -> Act:
     """AlexNet's MaxPool2d(3, 2) over a dense fp32 NHWC activation."""
@@ -247,6 +268,12 @@ class PerceptualLoss(nn.Module):
         """eval_models/__init__.py:26-40: pred, target fp32 [N,3,H,W] in [-1, 1] ([0, 1] with normalize) -> [N,1,1,1]."""
         with torch.no_grad():
             return self.net.forward(target, pred, normalize=normalize)
+
+    def forward_resized(self, pred, target, size=(128, 128)):
+        """train_generator.py:578 ``model.forward(T2(im), T2(output))`` with ``T2 = transforms.Resize((128, 128))``: both images
+        resized without antialiasing (PNetLin.forward_resized states the choice), then ``forward`` -> [N,1,1,1]."""
+        with torch.no_grad():
+            return self.net.forward_resized(target, pred, size=size)
 
     def forward_u8(self, pred_u8, target_u8) -> torch.Tensor:
         """evaluate.py's LPIPS of uint8 [N,H,W,3] images (T2 = ToTensor + Normalize(0.5, 0.5) fused into the input kernel) -> [N]."""

@@ -4,6 +4,8 @@
 ``skimage.metrics.structural_similarity(gt, pred, data_range=255, gaussian_weights=True, use_sample_covariance=False)``
 computes it (evaluate.py:67), and the MSE of ``ToTensor(gt)`` against ``ToTensor(pred)`` (evaluate.py:78-80).
 ``structural_similarity`` is the single-pair form with skimage's name; it accepts only the parameter set evaluate.py uses.
+``seg_iou_counts`` / ``seg_iou`` are train_condition.py's validation ``iou_metric`` (:18-36; csrc/validate.hip): the counts on the
+device in one launch, the ratio on the host.
 There is no CPU path: without libhrviton_hip.so these raise.
 """
 from __future__ import annotations
@@ -92,3 +94,47 @@ def structural_similarity(im1, im2, *, data_range=255, gaussian_weights=True, us
     b3 = _u8_cuda(b, "im2")[..., None].expand(*b.shape, 3).contiguous()
     ssim, _ = pair_stats(a3, b3)
     return float(ssim[0].item())
+
+
+COMPOSITIONS = {"no_composition": 0, "detach": 1, "warp_grad": 2}
+
+
+def seg_iou_counts(fake_segmap: torch.Tensor, warped_cm: Optional[torch.Tensor], label: torch.Tensor,
+                   composition: str = "warp_grad", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The counts behind train_condition.py's ``iou_metric(softmax(fake_segmap * cloth_mask, 1), label)`` (:18-36, 344-356) as an
+    int64 CUDA tensor [N,3]: per sample (intersection, sum_pred, sum_true) with ``pred = softmax > 0.5`` over all 13 channels and
+    pixels.  fake_segmap: fp32 [N,13,h,w] raw logits; warped_cm: fp32 [N,1,h,w] (unused and optional under 'no_composition');
+    label: fp32 one-hot [N,13,h,w].  ``out``: optional int64 CUDA buffer of at least N rows; rows [0, N) are overwritten (never
+    accumulated onto), later rows are left alone."""
+    if composition not in COMPOSITIONS:
+        raise ValueError(f"seg_iou_counts: composition {composition!r} is none of {sorted(COMPOSITIONS)}")
+    comp = COMPOSITIONS[composition]
+    for t, n in ((fake_segmap, "fake_segmap"), (label, "label")) + (((warped_cm, "warped_cm"),) if comp else ()):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 4:
+            raise HrvError(f"seg_iou_counts({n}): expected a 4-D fp32 CUDA tensor")
+    N, Cn, h, w = fake_segmap.shape
+    if Cn != 13 or tuple(label.shape) != (N, 13, h, w):
+        raise ValueError(f"seg_iou_counts: expected [N,13,h,w] logits and labels of one shape, got {tuple(fake_segmap.shape)} and "
+                         f"{tuple(label.shape)}")
+    if comp and tuple(warped_cm.shape) != (N, 1, h, w):
+        raise ValueError(f"seg_iou_counts: warped_cm {tuple(warped_cm.shape)} is not [{N},1,{h},{w}]")
+    seg, lab = fake_segmap.detach().contiguous(), label.detach().contiguous()
+    cm = warped_cm.detach().contiguous() if comp else None
+    if out is None:
+        out = torch.empty((N, 3), dtype=torch.int64, device=seg.device)
+    elif (not out.is_cuda or out.dtype != torch.int64 or out.dim() != 2 or out.shape[1] != 3 or out.shape[0] < N
+          or not out.is_contiguous()):
+        raise HrvError(f"seg_iou_counts(out): expected a contiguous int64 CUDA tensor [>={N},3]")
+    lib = _lib.load()
+    _lib.check(lib.hrv_seg_iou_nchw_f32(seg.data_ptr(), None if cm is None else cm.data_ptr(), lab.data_ptr(), N, h, w, comp,
+                                        out.data_ptr(), _stream()), "hrv_seg_iou_nchw_f32")
+    return out[:N]
+
+
+def seg_iou(counts) -> torch.Tensor:
+    """``(I + 1e-7) / (S_pred + S_true - I + 1e-7)`` per row of ``counts`` [N,3] = (I, S_pred, S_true), as a float64 CPU tensor [N].
+    The reference evaluates the same expression in fp32 on tensors (train_condition.py:31-35); from exact integer counts in
+    float64 the two agree to fp32 rounding."""
+    c = torch.as_tensor(counts).detach().to("cpu", torch.float64).reshape(-1, 3)
+    inter, union = c[:, 0], c[:, 1] + c[:, 2]
+    return (inter + 1e-7) / (union - inter + 1e-7)

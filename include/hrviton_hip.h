@@ -929,6 +929,21 @@ int hrv_pool3x3_nhwc_f32(const float* x, int32_t N, int32_t H, int32_t W, int32_
 int hrv_inception_head_f32(const float* feat, int32_t N, int32_t HW, int32_t C, int32_t cstride, const float* fc_w, const float* fc_b,
                            int32_t K, float* pooled, float* logits, float* probs, hrv_stream_t stream);
 
+/* ---- validation passes of the training scripts (validate.hip) ---- */
+/* The counts behind train_condition.py's iou_metric (:18-36), per sample, in one launch: seg fp32 NCHW [N,13,h,w] (raw logits), cm
+ * fp32 [N,1,h,w] (may be NULL when comp == 0), label fp32 NCHW [N,13,h,w] (one-hot).  comp 0: no_composition; 1: detach (channel 3
+ * times cm > 0.5); 2: warp_grad (channel 3 times cm).  pred = softmax_c(seg * mask) > 0.5 (strict; fp32: subtract the channel
+ * maximum, expf, sum in channel order, divide) over all 13 channels and pixels.  out int64 [N,3] = (count of pred && label == 1,
+ * count of pred, count of label == 1); the entry zeroes out[0 .. 3N) in-stream first and adds with integer atomics, so the result
+ * does not depend on what the buffer held or on scheduling. */
+int hrv_seg_iou_nchw_f32(const float* seg, const float* cm, const float* label, int32_t N, int32_t h, int32_t w, int32_t comp,
+                         int64_t* out, hrv_stream_t stream);
+/* LPIPS input with the resize folded in: in0, in1 fp32 NCHW [N,3,H,W] -> out fp32 NHWC [2N,Ho,Wo,4] (in0's images first), each
+ * bilinearly resampled (align_corners=False, no antialiasing) and passed through (v - shift[c]) / scale[c] (2v - 1 first when
+ * normalize != 0), channel 3 zero: bit for bit hrv_resize_nchw_f32 followed by hrv_lpips_prep_nchw_f32, in one launch. */
+int hrv_lpips_prep_resize_nchw_f32(const float* in0, const float* in1, int32_t N, int32_t H, int32_t W, int32_t Ho, int32_t Wo,
+                                   int32_t normalize, const float* shift3, const float* scale3, float* out, hrv_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,10 @@
    algorithmic FLOPs, 11.4 GFLOP = 5.7 G multiply-adds per image, over the sum of their event times);
 4. a full evaluate.py run over N synthetic 1024x768 JPEG pairs in a child process: wall time split into time blocked on the
    DataLoader (CPU decode / resize) and time in the GPU scorer.
+5. the validation passes' kernels (csrc/validate.hip): LPIPS of two 1024x768 fp32 images resized to 128x128, fused front end
+   (``forward_resized``: one launch for both resizes and ScalingLayers) against the unfused one (``forward`` of two
+   ``glue.resize_nchw`` results: four launches and a round trip), batch 1 and B, whole call and front end alone; and the IoU count
+   kernel at 8 x 256 x 192 and 4 x 1024 x 768 as bytes (108 per pixel) over event time.
 Event times include launch gaps; for kernel-only times run this under ``rocprofv3 --kernel-trace --stats`` in a run of its own.
 Prints one JSON line.
 """
@@ -84,6 +88,44 @@ def inception_bench(B, reps):
     return out
 
 
+def validation_bench(B, reps):
+    from hr_viton_amd import _lib, glue
+    torch.manual_seed(0)
+    net = PerceptualLoss().net
+    _, _, (sh, sc) = net.plan(torch.device("cuda"))
+    lib = _lib.load()
+    g = torch.Generator(device="cuda").manual_seed(2)
+    out = {"lpips_resized_1024x768": {}, "seg_iou": {}}
+    for b in sorted({1, B}):
+        x = torch.rand(b, 3, 1024, 768, device="cuda", generator=g) * 2 - 1
+        y = torch.rand(b, 3, 1024, 768, device="cuda", generator=g) * 2 - 1
+        both = torch.empty(2 * b, 128, 128, 4, device="cuda")
+
+        def front_fused():
+            lib.hrv_lpips_prep_resize_nchw_f32(x.data_ptr(), y.data_ptr(), b, 1024, 768, 128, 128, 0, sh, sc, both.data_ptr(),
+                                               ops._stream())
+
+        def front_unfused():
+            for i, t in enumerate((x, y)):
+                r = glue.resize_nchw(t, (128, 128))
+                lib.hrv_lpips_prep_nchw_f32(r.data_ptr(), b, 128, 128, 0, sh, sc, both[i * b:].data_ptr(), ops._stream())
+
+        out["lpips_resized_1024x768"][f"batch_{b}"] = {
+            "fused_us_per_pair": 1e6 * timed(lambda: net.forward_resized(x, y), reps) / b,
+            "unfused_us_per_pair": 1e6 * timed(lambda: net.forward(glue.resize_nchw(x, (128, 128)), glue.resize_nchw(y, (128, 128))),
+                                               reps) / b,
+            "front_end_fused_us": 1e6 * timed(front_fused, reps), "front_end_unfused_us": 1e6 * timed(front_unfused, reps)}
+    for n, h, w in ((8, 256, 192), (4, 1024, 768)):
+        seg = torch.randn(n, 13, h, w, device="cuda", generator=g) * 4
+        cm = torch.rand(n, 1, h, w, device="cuda", generator=g)
+        lab = torch.zeros(n, 13, h, w, device="cuda").scatter_(1, torch.randint(0, 13, (n, 1, h, w), device="cuda", generator=g), 1.0)
+        cnt = torch.empty(n, 3, dtype=torch.int64, device="cuda")
+        t = timed(lambda: metrics.seg_iou_counts(seg, cm, lab, "warp_grad", out=cnt), reps)
+        out["seg_iou"][f"{n}x{h}x{w}"] = {"us": 1e6 * t, "gb_per_s": 108.0 * n * h * w / t / 1e9,
+                                          "fraction_of_copy_rate": 108.0 * n * h * w / t / HBM_BPS}
+    return out
+
+
 def e2e(n, workers, batch):
     from PIL import Image
     rng = np.random.default_rng(0)
@@ -134,7 +176,7 @@ def main():
                           "byte_floor_ms_per_pair": 1e3 * fb / B, "valu_floor_ms_per_pair": 1e3 * ff / B,
                           "fraction_of_floor": floor / t_ps},
            "lpips_128": {"B": B, "ms_per_pair": 1e3 * t_lp / B},
-           "inception_299": inception_bench(B, a.reps)}
+           "inception_299": inception_bench(B, a.reps), "validation": validation_bench(B, a.reps)}
     if a.e2e:
         res["evaluate_py"] = e2e(a.e2e, a.workers, B)
     print(json.dumps(res))

@@ -9,8 +9,12 @@ kernels (hr_viton_amd.cond_train, .functional, .losses, .vgg); one iteration is
     ``-b`` is the GLOBAL batch, split over the ranks; BatchNorm uses per-GPU batch statistics
     (the north star replaces sync_batchnorm by per-GPU BN) and gradients are bucket-all-reduced
     on RCCL during the backward (hr_viton_amd.parallel.GradSync).
-  * ``--synthetic`` feeds VITON-HD-shaped random batches (no dataset / torchvision in this image);
-    the tensorboard / validation-IoU blocks (train_condition.py:311-418) are out of scope.
+  * ``--synthetic`` feeds VITON-HD-shaped random batches (no dataset / torchvision in this image).
+  * validation (train_condition.py:313-360): every ``--val_count`` steps rank 0 scores the first ``--val_items`` items of the test
+    list (``--test_dataroot`` / ``--test_data_list``; fixed-seed synthetic batches under ``--synthetic``) with tocg in eval mode and
+    logs ``val/iou`` to ``<tensorboard_dir>/<name>/scalars.jsonl`` (and to tensorboard where a SummaryWriter is importable):
+    hr_viton_amd.validate, which states the deviations.  The tensorboard loss scalars and image grids (``visualize_segmap``,
+    :362-418) are out of scope.
   * --warp_feature encoder / --out_layer conv (networks.py:46-61,142-144) and --upsample nearest (the inter-flow loss's flow
     resize, train_condition.py:242 -- the only place the reference's scripts use the flag) are on the HIP path (round 5).
 """
@@ -35,6 +39,7 @@ from hr_viton_amd.networks import (ConditionGenerator, GANLoss, VGGLoss, define_
 from hr_viton_amd.optim import Adam  # noqa: E402
 from hr_viton_amd.parallel import broadcast_module  # noqa: E402
 from hr_viton_amd.pipeline import condition_train_step  # noqa: E402
+from hr_viton_amd.validate import ScalarLog, condition_validation_iou, val_items_loader, validation_due  # noqa: E402
 
 
 def get_opt(argv=None):
@@ -97,6 +102,7 @@ def get_opt(argv=None):
     p.add_argument("--vgg_random_init", action="store_true",
                    help="plumbing / bench runs only: a RANDOMLY initialised VGG19 in the perceptual loss (no network here to "
                         "download the pretrained weights); implied by --synthetic")
+    p.add_argument("--val_items", type=int, default=2000, help="test items scored per val/iou pass (the reference's 2000)")
     opt = p.parse_args(argv)
     return opt
 
@@ -133,6 +139,36 @@ def disk_batch(inputs, device):
             "parse_agnostic": inputs["parse_agnostic"].to(device), "densepose": inputs["densepose"].to(device),
             "parse_onehot": inputs["parse_onehot"].to(device), "parse": inputs["parse"].to(device),
             "pcm": inputs["pcm"].to(device), "parse_cloth": inputs["parse_cloth"].to(device)}
+
+
+VAL_SEED = 7_000_003      # synthetic validation batches: the same draws at every pass, so the series is comparable over a run
+
+
+class _Validation(object):
+    """The val/iou pass of one run: the test loader is built at first use, the log at the first record."""
+
+    def __init__(self, opt, device):
+        self.opt, self.device = opt, device
+        self.loader = None
+        self.board = ScalarLog(os.path.join(opt.tensorboard_dir, opt.name))
+
+    def batches(self):
+        opt = self.opt
+        if opt.synthetic:
+            for k in range(-(-opt.val_items // opt.batch_size)):
+                yield synthetic_batch(opt, opt.batch_size, VAL_SEED + k, self.device)
+            return
+        if self.loader is None:
+            self.loader, _ = val_items_loader(opt, opt.val_items, opt.batch_size)
+        for inputs in self.loader:
+            yield disk_batch(inputs, self.device)
+
+    def run(self, tocg, step):
+        res = condition_validation_iou(self.opt, tocg, self.batches(), max_items=self.opt.val_items)
+        if res["items"]:
+            self.board.add_scalar("val/iou", res["iou"], step + 1)
+            print("step: %8d, val/iou: %.6f (%d items)" % (step + 1, res["iou"], res["items"]), flush=True)
+        return res
 
 
 def main(argv=None):
@@ -187,6 +223,7 @@ def main(argv=None):
     if not opt.synthetic:
         loader = _rank_loader(opt, per_rank, rank, world)
     last = opt.keep_step if not opt.max_steps else min(opt.keep_step, opt.load_step + opt.max_steps)
+    validation = _Validation(opt, dev) if rank == 0 else None
     for step in range(opt.load_step, last):
         t0 = time.time()
         if loader is None:
@@ -194,6 +231,8 @@ def main(argv=None):
         else:
             batch = disk_batch(loader.next_batch(), dev)
         losses = condition_train_step(opt, tocg, D, crit_l1, crit_vgg, crit_gan, opt_g, opt_d, batch, sync_g, sync_d)
+        if validation_due(step, opt.val_count) and validation is not None:          # :313-360
+            validation.run(tocg, step)
         if (step + 1) % opt.display_count == 0 and rank == 0:
             torch.cuda.synchronize()
             t = time.time() - t0
@@ -208,6 +247,7 @@ def main(argv=None):
     if rank == 0:
         save_checkpoint(tocg, os.path.join(opt.checkpoint_dir, opt.name, "tocg_final.pth"), opt)
         save_checkpoint(D, os.path.join(opt.checkpoint_dir, opt.name, "D_final.pth"), opt)
+        validation.board.close()
         print("Finished training %s!" % opt.name)
 
 

@@ -10,8 +10,14 @@ on the MI355X-native hot path.
   * ``--fp16``: mixed precision like the reference's apex O1 -- every training convolution (forward, data and
     weight gradient) runs on the bf16 matrix cores over fp32 tensors (hr_viton_amd.train_ops.MMA_BF16);
     normalisations, losses, the optimizer and everything in HBM stay fp32.
-  * ``--synthetic`` feeds VITON-HD-shaped random batches (no dataset / torchvision in this image);
-    tensorboard / LPIPS evaluation blocks (train_generator.py:364-584) are out of scope.
+  * ``--synthetic`` feeds VITON-HD-shaped random batches (no dataset / torchvision in this image).
+  * LPIPS evaluation (train_generator.py:480-584): every ``--lpips_count`` steps rank 0 runs the frozen pipeline and the generator in
+    eval mode over the first ``--val_items`` items of the test list (``--test_dataroot`` / ``--test_data_list``; fixed-seed synthetic
+    batches under ``--synthetic``), batch ``--val_batch_size``, and logs ``test/LPIPS`` of the 128x128 resizes to
+    ``<tensorboard_dir>/<name>/scalars.jsonl`` (and to tensorboard where a SummaryWriter is importable): hr_viton_amd.validate,
+    which states the deviations.  The LPIPS weights are read from ``--lpips_weights`` / ``--alexnet_weights`` and never downloaded;
+    where they are missing the pass is skipped with one note.  The tensorboard loss scalars and image grids (``make_image_grid``,
+    :364-478) are out of scope.
 Bug-fixes of the reference call sites: tocg(input1, input2) arity, load_checkpoint arity,
 Adam betas as floats.
 """
@@ -37,6 +43,8 @@ from hr_viton_amd.networks import ConditionGenerator  # noqa: E402
 from hr_viton_amd.optim import Adam  # noqa: E402
 from hr_viton_amd.parallel import broadcast_module  # noqa: E402
 from hr_viton_amd.pipeline import generator_train_step, make_generator_inputs  # noqa: E402
+from hr_viton_amd.validate import (ScalarLog, generator_validation_lpips, load_validation_lpips, val_items_loader,  # noqa: E402
+                                   validation_due)
 from hr_viton_amd.vgg import VGGLoss  # noqa: E402
 
 
@@ -105,6 +113,13 @@ def get_opt(argv=None):
     p.add_argument("--vgg_random_init", action="store_true",
                    help="plumbing / bench runs only: a RANDOMLY initialised VGG19 in the perceptual loss (no network here to "
                         "download the pretrained weights); implied by --synthetic")
+    p.add_argument("--lpips_weights", default="./eval_models/weights/v0.1/alex.pth", help="LPIPS v0.1 lin layers (alex.pth)")
+    p.add_argument("--alexnet_weights", default=None,
+                   help="torchvision alexnet state dict (default: torch's hub cache; read only if present)")
+    p.add_argument("--lpips_random_init", action="store_true",
+                   help="plumbing only: test/LPIPS on randomly initialised AlexNet / lin weights (labelled); implied by --synthetic")
+    p.add_argument("--val_items", type=int, default=500, help="test items scored per test/LPIPS pass (the reference's 500)")
+    p.add_argument("--val_batch_size", type=int, default=1, help="batch of the test/LPIPS pass (the reference's 1)")
     opt = p.parse_args(argv)
     opt.gpu_ids = [int(s) for s in str(opt.gpu_ids).split(",") if s.strip() and int(s) >= 0]
     return opt
@@ -119,6 +134,51 @@ def synthetic_batch(opt, n, seed, device):
     return {"cloth": u(3), "cloth_mask": (torch.rand(n, 1, H, W, generator=g) > 0.4).float().to(device),
             "parse_agnostic": onehot, "densepose": u(3), "agnostic": u(3), "image": u(3),
             "parse": onehot, "parse_cloth": u(3)}
+
+
+VAL_SEED = 9_000_011      # synthetic validation batches: the same draws at every pass, so the series is comparable over a run
+
+
+def disk_batch(raw, dev):
+    """cp_dataset.py batch -> the flat dictionary make_generator_inputs takes (train_generator.py:194-212)."""
+    return {"cloth": raw["cloth"]["paired"].to(dev), "cloth_mask": raw["cloth_mask"]["paired"].to(dev),
+            "parse_agnostic": raw["parse_agnostic"].to(dev), "densepose": raw["densepose"].to(dev),
+            "agnostic": raw["agnostic"].to(dev), "image": raw["image"].to(dev),
+            "parse": raw["parse"].to(dev), "parse_cloth": raw["parse_cloth"].to(dev)}
+
+
+class _Validation(object):
+    """The test/LPIPS pass of one run: LPIPS model and test loader are built at first use, the log at the first record."""
+
+    def __init__(self, opt, device):
+        self.opt, self.device = opt, device
+        self.loader, self.model, self.tried = None, None, False
+        self.board = ScalarLog(os.path.join(opt.tensorboard_dir, opt.name))
+
+    def batches(self):
+        opt, bs = self.opt, max(1, self.opt.val_batch_size)
+        if opt.synthetic:
+            for k in range(-(-opt.val_items // bs)):
+                yield synthetic_batch(opt, bs, VAL_SEED + k, self.device)
+            return
+        if self.loader is None:
+            self.loader, _ = val_items_loader(opt, opt.val_items, bs)
+        for raw in self.loader:
+            yield disk_batch(raw, self.device)
+
+    def run(self, tocg, generator, step):
+        if not self.tried:
+            self.tried = True
+            self.model = load_validation_lpips(self.opt)       # None, with one note, when the weights are missing
+        if self.model is None:
+            return None
+        print("LPIPS")
+        res = generator_validation_lpips(self.opt, tocg, generator, self.model, self.batches(), max_items=self.opt.val_items)
+        if res["items"]:
+            avg_distance = res["lpips"]
+            print(f"LPIPS{avg_distance}")
+            self.board.add_scalar("test/LPIPS", avg_distance, step + 1)
+        return res
 
 
 def main(argv=None):
@@ -195,19 +255,18 @@ def main(argv=None):
     last = opt.keep_step + opt.decay_step
     if opt.max_steps:
         last = min(last, opt.load_step + opt.max_steps)
+    validation = _Validation(opt, dev) if rank == 0 else None
     for step in range(opt.load_step, last):
         t0 = time.time()
         if loader is None:
             batch = synthetic_batch(opt, per_rank, hdist.shard_seed(1234 + step * 97, rank), dev)
         else:
-            raw = loader.next_batch()                                  # train_generator.py:194-212
-            batch = {"cloth": raw["cloth"]["paired"].to(dev), "cloth_mask": raw["cloth_mask"]["paired"].to(dev),
-                     "parse_agnostic": raw["parse_agnostic"].to(dev), "densepose": raw["densepose"].to(dev),
-                     "agnostic": raw["agnostic"].to(dev), "image": raw["image"].to(dev),
-                     "parse": raw["parse"].to(dev), "parse_cloth": raw["parse_cloth"].to(dev)}
+            batch = disk_batch(loader.next_batch(), dev)               # train_generator.py:194-212
         x, parse7 = make_generator_inputs(opt, tocg, batch)
         losses, _ = generator_train_step(opt, generator, discriminator, crit_gan, crit_feat, crit_vgg, opt_g, opt_d, x,
                                          parse7, batch["image"], sync_g, sync_d)
+        if validation_due(step, opt.lpips_count) and validation is not None:        # :480-584
+            validation.run(tocg, generator, step)
         if (step + 1) % opt.display_count == 0 and rank == 0:
             torch.cuda.synchronize()
             t = time.time() - t0
@@ -224,6 +283,7 @@ def main(argv=None):
     if rank == 0:
         save_checkpoint(generator, os.path.join(opt.checkpoint_dir, opt.name, "gen_model_final.pth"), opt)
         save_checkpoint(discriminator, os.path.join(opt.checkpoint_dir, opt.name, "dis_model_final.pth"), opt)
+        validation.board.close()
         print("Finished training %s!" % opt.name)
 
 
