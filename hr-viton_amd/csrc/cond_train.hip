@@ -8,15 +8,11 @@
 
 namespace hrv {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 static inline int grid_for(size_t work, int block = 256) {
   size_t g = (work + block - 1) / block;
   const size_t cap = 256 * 16;
   return (int)(g < 1 ? 1 : (g > cap ? cap : g));
 }
-
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 
 // ---------------------------------------------------------------------------
 // BatchNorm2d, training mode.  Per-sample (mean, rstd) come from

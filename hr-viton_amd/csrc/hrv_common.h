@@ -50,6 +50,28 @@ __device__ __forceinline__ float apply_act(float v, int act, float slope) {
   }
 }
 
+// derivative of ReLU / LeakyReLU expressed through the activation's OUTPUT y
+__device__ __forceinline__ float dact(float y, int act, float slope) {
+  if (act == HRV_ACT_RELU) return y > 0.f ? 1.f : 0.f;
+  if (act == HRV_ACT_LRELU) return y > 0.f ? 1.f : slope;
+  return 1.f;
+}
+
+// four consecutive channels of an NHWC tensor, stored as fp32 (16 bytes) or bf16 (8 bytes; `elem` counts elements from `base`)
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x4t __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+__device__ __forceinline__ f32x4 ld4_bf16(const void* base, size_t elem) {
+  const uint2 u = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(base) + elem);
+  f32x4 v;
+  v[0] = __builtin_bit_cast(float, u.x << 16); v[1] = __builtin_bit_cast(float, u.x & 0xFFFF0000u);
+  v[2] = __builtin_bit_cast(float, u.y << 16); v[3] = __builtin_bit_cast(float, u.y & 0xFFFF0000u);
+  return v;
+}
+__device__ __forceinline__ void st4_bf16(void* base, size_t elem, f32x4 v) {
+  *reinterpret_cast<bf16x4t*>(reinterpret_cast<unsigned short*>(base) + elem) = __builtin_convertvector(v, bf16x4t);
+}
+
 // Bijective XCD-aware remap: hardware places block b on XCD b % 8; give each XCD
 // a contiguous range of logical tiles so neighbouring tiles (shared halo rows,
 // shared weight panels) hit the same 4 MiB L2.  Speed only, never correctness.

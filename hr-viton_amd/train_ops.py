@@ -654,7 +654,7 @@ def colsum(a: Act, out: Optional[torch.Tensor] = None, accumulate: bool = False)
 
 
 # ---------------------------------------------------------------------------------------------
-# HBM-bound training kernels (train.hip)
+# HBM-bound training kernels (norm_bwd.hip, train.hip)
 # ---------------------------------------------------------------------------------------------
 def _norm_bwd_desc(x, mean, rstd, dout, act, slope, out, g1p, z, noise_scale, want_dgb, dx, dx_accumulate, dnoise_scale, dns_accumulate,
                    dgb_bf16, dx_bf16, dgb=None):

@@ -254,7 +254,7 @@ int hrv_conv2d_wgrad_bf16mma_st_nhwc_f32(const void* dy, int32_t dy_cstride, int
 int hrv_colsum_nhwc_f32(const float* x, int64_t P, int32_t C, int32_t cstride, int32_t coff, float* workspace,
                         int64_t workspace_bytes, float* out, int32_t accumulate, hrv_stream_t stream);
 
-/* ---- training side, HBM-bound kernels (train.hip) -------------------------
+/* ---- training side, HBM-bound kernels (norm_bwd.hip, train.hip) -------------------------
  * SPADE / InstanceNorm backward (network_generator.py:101-122 + LeakyReLU :170-171;
  * PatchGAN IN+LeakyReLU :263-272) for
  *     v = x + noise_z*noise_scale;  nh = (v - mean)*rstd;  out = act(nh*g1p + beta)

@@ -1,4 +1,4 @@
-"""The storage forms of the SPADE / InstanceNorm backward that have compile-time instances (csrc/train.hip), as
+"""The storage forms of the SPADE / InstanceNorm backward that have compile-time instances (csrc/norm_bwd.hip), as
 descriptor recipes: one case per combination of a stage-1 and a stage-2 instance the training step meets, the two pair forms, and
 descriptors outside the table.  ``hits``: the lines of hrv_diag_norm_bwd_instances() a case runs on.  Shared by the CPU test (the
 table in C, the list in DESIGN.md and these cases name the same instances) and the GPU test (each instance against the generic
@@ -42,6 +42,14 @@ CASES = [
 
 # (N, H, W, C): a small extent, and two whose H*W is not a multiple of the 128-pixel slab; H and W even (the up-sampled source)
 EXTENTS = [(2, 16, 16, 64), (1, 18, 14, 80), (2, 34, 22, 128)]
+
+# The pair pass against two sequential single calls (tests/test_gpu_spade_fused.py), N = 2: (H, W, up).  9x15 = 135 pixels are two
+# slabs of 68 and 67 (norm_slabs does not divide H*W); 6x10 is even in both directions for the up-sampled source.  PAIR_CHANNELS:
+# C/4 = 3 (85 pixel rows in flight: a thread walks one pixel at most, the tail alone) and C/4 = 65, one over NORM_GCAP: a second
+# channel chunk with one live group, four rows, each thread walking 17 or 15 pixels at 9x15 -- the single's two-pixel stage-1
+# loop runs and then takes its one-pixel tail (tests/test_norm_bwd_instances_cpu.py checks these properties).
+PAIR_EXTENTS = [(9, 15, False), (6, 10, True)]
+PAIR_CHANNELS = [12, 260]
 
 
 def instance_lines():

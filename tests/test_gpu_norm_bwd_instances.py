@@ -1,4 +1,4 @@
-"""Every compile-time instance of the SPADE / InstanceNorm backward (csrc/train.hip) against the generic run-time
+"""Every compile-time instance of the SPADE / InstanceNorm backward (csrc/norm_bwd.hip) against the generic run-time
 kernels on the same descriptor: HRV_NORM_BWD_GENERIC=1 forces the generic kernels, which are the kernels every result came from
 before the instances existed.  Same statements in the same order, so every output is compared with torch.equal -- dx, dnh,
 [dgamma | dbeta], the noise-scale gradient and the whole workspace (slab partials, m1 / m2 rows) -- including the poisoned pad

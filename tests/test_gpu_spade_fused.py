@@ -9,6 +9,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import norm_bwd_instance_cases as K
+
 pytestmark = pytest.mark.gpu
 
 
@@ -284,3 +286,65 @@ def test_one_pass_backward_of_the_two_norms_over_the_block_input_is_bit_identica
             assert torch.equal(a[1][k], b[1][k]), k
     finally:
         T.MMA_BF16[0] = False
+
+
+def _pair_arm(kinds, Cn, H, W, up, paired, generic, monkeypatch):
+    """norm a and norm b (``kinds``: "spade" with noise, "inorm" without) over one x, as the pair call or as two single calls with
+    dx_accumulate on the second -> every output tensor, padding included"""
+    import ctypes as C
+    from test_gpu_norm_bwd_instances import _Buf, _one_norm
+    from hr_viton_amd import _lib
+    lib = _lib.load()
+    monkeypatch.setenv("HRV_NORM_BWD_GENERIC", "1" if generic else "0")
+    _lib.reload_env()
+    N = 2
+    g = torch.Generator(device="cuda").manual_seed(5)
+    rnd = lambda *s_: torch.randn(*s_, device="cuda", generator=g)
+    if up:
+        x = (_Buf(N, H // 2, W // 2, Cn - 4, False, fill=rnd(N, H // 2, W // 2, Cn - 4)), _Buf(N, H, W, 4, False, fill=rnd(N, H, W, 4)))
+    else:
+        x = _Buf(N, H, W, Cn, False, fill=rnd(N, H, W, Cn))
+    dx = _Buf(N, H, W, Cn, False)
+    case = lambda kind, dx_: K.Case("pair_vs_two", kind, "bf16" if up else "f32", "f32", up, dx_, paired, None, ())
+    da, outs_a, flat_a, keep_a = _one_norm(case(kinds[0], "f32"), N, H, W, Cn, 21, x, dx)
+    db, outs_b, flat_b, keep_b = _one_norm(case(kinds[1], "f32" if paired else "acc"), N, H, W, Cn, 22, x, dx)
+    if paired:
+        route = lib.hrv_diag_norm_bwd_route(C.byref(da), C.byref(db))
+        _lib.check(lib.hrv_spade_norm_bwd2_nhwc_f32(C.byref(da), C.byref(db), None), "hrv_spade_norm_bwd2_nhwc_f32")
+    else:
+        route = lib.hrv_diag_norm_bwd_route(C.byref(da), None) & lib.hrv_diag_norm_bwd_route(C.byref(db), None)
+        _lib.check(lib.hrv_spade_norm_bwd_nhwc_f32(C.byref(da), None), "hrv_spade_norm_bwd_nhwc_f32 (a)")
+        _lib.check(lib.hrv_spade_norm_bwd_nhwc_f32(C.byref(db), None), "hrv_spade_norm_bwd_nhwc_f32 (b)")
+    torch.cuda.synchronize()
+    outs_b.pop("dx")
+    res = {"dx": dx.t}
+    for tag, outs, flat in (("a", outs_a, flat_a), ("b", outs_b, flat_b)):
+        res.update({f"{tag}.{k}": b_.t for k, b_ in outs.items() if k != "dx"})
+        res.update({f"{tag}.{k}": t for k, t in flat.items() if k != "workspace"})
+    return route, res
+
+
+@pytest.mark.parametrize("generic", [True, False], ids=["generic_kernels", "instances"])
+@pytest.mark.parametrize("kinds", [("spade", "spade"), ("spade", "inorm")], ids=["both_with_noise", "noise_and_none"])
+@pytest.mark.parametrize("Cn", K.PAIR_CHANNELS)
+@pytest.mark.parametrize("H,W,up", K.PAIR_EXTENTS, ids=[f"{h}x{w}" + ("_upsampled" if u else "") for h, w, u in K.PAIR_EXTENTS])
+def test_the_pair_call_equals_two_single_calls_bit_for_bit(monkeypatch, H, W, up, Cn, kinds, generic):
+    """hrv_spade_norm_bwd2_nhwc_f32 against hrv_spade_norm_bwd_nhwc_f32 twice, dx_accumulate on the second: dx, both dnh, both
+    [dgamma | dbeta] and both noise-scale gradients with torch.equal (padding included), on the generic kernels and on the
+    instances.  The extents (norm_bwd_instance_cases.PAIR_*; their properties are checked on the CPU) reach the one-pixel tail of
+    the single's two-pixel loop, a slab count that does not divide H*W, one channel chunk with idle threads and a second chunk
+    with one live group, and the up-sampled source; ``noise_and_none`` pairs a SPADE norm with a plain InstanceNorm + LeakyReLU
+    (no noise, no 1 + gamma, no dgb), which only the generic pair kernels serve."""
+    import hr_viton_amd  # noqa: F401
+    route_2, want = _pair_arm(kinds, Cn, H, W, up, False, generic, monkeypatch)
+    route_p, got = _pair_arm(kinds, Cn, H, W, up, True, generic, monkeypatch)
+    if generic or kinds[0] != kinds[1]:
+        assert route_p == 0, "the generic pair kernels"
+    else:
+        assert route_p == 3 and route_2 == 3, "both stages of the pair and of the single calls on an instance"
+    assert want.keys() == got.keys() and {"dx", "a.dnh", "b.dnh", "a.dgb", "a.dnoise_scale"} <= want.keys()
+    assert (kinds[1] == "spade") == ("b.dgb" in want) == ("b.dnoise_scale" in want)
+    for k in want:
+        assert not torch.isnan(want[k].float()).any(), k
+        assert torch.equal(want[k], got[k]), f"{k}: {int((want[k] != got[k]).sum())} of {want[k].numel()} elements differ"
+    assert not bool((got["dx"][..., 4:4 + Cn] == 1.5e4).any()), "dx was written"
