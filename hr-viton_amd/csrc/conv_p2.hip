@@ -23,34 +23,6 @@
 
 namespace hrv {
 
-#if defined(__HIP_DEVICE_COMPILE__)
-__device__ __forceinline__ void p2_store16(f32x4 v, rsrc_t r, unsigned voff) {
-  typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), r, (int)voff, 0, 0);
-}
-typedef unsigned p2_u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ p2_u32x2 p2_load8(rsrc_t r, unsigned voff, int soff) { return __builtin_amdgcn_raw_buffer_load_b64(r, (int)voff, soff, 0); }
-__device__ __forceinline__ f32x4 p2_load16(rsrc_t r, unsigned voff, int soff) {
-  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, soff, 0));
-}
-// v_permlane32_swap: lanes 0..31 of the result pair hold (lo, lo of lane + 32), lanes 32..63 hold (hi of lane - 32, hi)
-__device__ __forceinline__ p2_u32x2 p2_swap32(unsigned lo, unsigned hi) {
-  const auto s = __builtin_amdgcn_permlane32_swap(lo, hi, false, false);
-  p2_u32x2 r;
-  r[0] = s[0]; r[1] = s[1];
-  return r;
-}
-// (by value: __builtin_bit_cast applied to a vector ELEMENT expression reads element 0 whatever the index)
-__device__ __forceinline__ unsigned p2_bits(float f) { return __builtin_bit_cast(unsigned, f); }
-#else
-__device__ inline void p2_store16(f32x4, rsrc_t, unsigned) {}
-typedef unsigned p2_u32x2 __attribute__((ext_vector_type(2)));
-__device__ inline p2_u32x2 p2_load8(rsrc_t, unsigned, int) { return p2_u32x2{0, 0}; }
-__device__ inline f32x4 p2_load16(rsrc_t, unsigned, int) { return f32x4{0.f, 0.f, 0.f, 0.f}; }
-__device__ inline p2_u32x2 p2_swap32(unsigned a, unsigned b) { return p2_u32x2{a, b}; }
-__device__ inline unsigned p2_bits(float) { return 0u; }
-#endif
-
 __device__ __forceinline__ f32x4 p2_acc4(const f32x16& a, int g) {
   f32x4 r;
   r[0] = a[4 * g]; r[1] = a[4 * g + 1]; r[2] = a[4 * g + 2]; r[3] = a[4 * g + 3];
@@ -176,8 +148,6 @@ __global__ __launch_bounds__(256) void p2_pack_kernel(const P2PackParams p) {
 }
 
 // ------------------------------------------------------------------------------------------------ the kernel
-constexpr int p2_wait(int vm) { return (vm & 15) | (7 << 4) | (0 << 8) | ((vm >> 4) << 14); }   // vmcnt(vm) lgkmcnt(0)
-
 struct P2Tile { int n, y0, x0; };
 __device__ __forceinline__ P2Tile p2_tile(const P2Params& p, int bid) {
   const int tx = (p.W + 15) >> 4, ty = (p.H + 15) >> 4;
@@ -205,11 +175,7 @@ __device__ __forceinline__ void p2_patch_piece(const P2Params& p, unsigned char*
   const int gs = g ^ ((hx >> 2) & 3);
   const bool ok = hy < 18 && hx < 18 && (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W && chunk * 32 + gs * 8 < p.Cin;
   const unsigned off = ((unsigned)(y * p.W + x) * (unsigned)p.src_cs + (unsigned)(p.src_co + chunk * 32 + gs * 8)) * 2u;
-#ifdef P2_EXP_L2PATCH      // timing experiment only (wrong results): every patch piece reads the same 23 KB -- L2 hits, same instruction stream
-  dma16(a_rsrc, reinterpret_cast<float*>(smem + p2_patch_off(NTP) + buf * P2_PBUF + pp * 1024), (unsigned)(pp * 1024 + lane * 16), 0u);
-#else
   dma16(a_rsrc, reinterpret_cast<float*>(smem + p2_patch_off(NTP) + buf * P2_PBUF + pp * 1024), ok ? off : 0xFFFFFFF0u, 0u);
-#endif
 }
 
 // The head of a (tile, pass): chunk 0 of the patch -> buffer 0 (6 pieces per wave), k-tiles 0 / 1 -> ring stages 0 / 1.
@@ -261,7 +227,7 @@ __device__ __forceinline__ void p2_pass(const P2Params& p, const int pass, unsig
   };
 
   // every wave is done with the previous (tile, pass): its epilogue's staging scratch lives in patch buffer 1, its bias in cbuf
-  __builtin_amdgcn_s_waitcnt(p2_wait(63));
+  __builtin_amdgcn_s_waitcnt(wait_vm(63));
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
   if (p.tlog && tid == 0 && first) p.tlog[(size_t)bid * 8 + 0] = wall_clock64();
@@ -277,9 +243,9 @@ __device__ __forceinline__ void p2_pass(const P2Params& p, const int pass, unsig
 
   // The head (chunk 0, k-tiles 0 and 1) has landed.  Behind it in this wave's queue sit only the previous pass's epilogue
   // stores (they need not drain) -- unless this pass loaded constants or is the block's first
-  if (wait_all || load_consts) __builtin_amdgcn_s_waitcnt(p2_wait(0));
-  else if (p.out_f32) __builtin_amdgcn_s_waitcnt(p2_wait(2 * NST));
-  else __builtin_amdgcn_s_waitcnt(p2_wait(NST));
+  if (wait_all || load_consts) __builtin_amdgcn_s_waitcnt(wait_vm(0));
+  else if (p.out_f32) __builtin_amdgcn_s_waitcnt(wait_vm(2 * NST));
+  else __builtin_amdgcn_s_waitcnt(wait_vm(NST));
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
   // the accumulators start at the bias (cbuf: this pass's columns, zeros without a bias; published by the barrier above)
@@ -333,11 +299,9 @@ __device__ __forceinline__ void p2_pass(const P2Params& p, const int pass, unsig
   // rides in the instruction's scalar offset; columns beyond Cout read whatever lies there (at worst zeros past the end of the
   // tensor): those lanes store nothing.  EPI == 1 requests column tile 0 under the LAST chunk's tap 6 (the loads are younger
   // than every LDS-DMA piece of the pass: the counted waits behind them allow 8 more in flight) and double-buffers the rest.
-  typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-  typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
   constexpr unsigned P2_OOB = 0xF0000000u;
   constexpr bool MASK_EARLY = EPI == 1;
-  u32x2_t mv[2][2][4];
+  u32x2 mv[2][2][4];
   unsigned moff[2] = {P2_OOB, P2_OOB};
   rsrc_t m_rsrc = make_rsrc(nullptr, 0u);
   auto mask_setup = [&]() {
@@ -351,11 +315,11 @@ __device__ __forceinline__ void p2_pass(const P2Params& p, const int pass, unsig
       moff[i] = (py < p.H && pxm < p.W) ? ((unsigned)(py * p.W + pxm) * (unsigned)p.mask_cs + (unsigned)(p.mask_co + tile0 * 32 + 4 * (lane_m >> 5))) * 2u : P2_OOB;
     }
   };
-  auto load_mask = [&](const int j, u32x2_t (&m)[2][4]) {
+  auto load_mask = [&](const int j, u32x2 (&m)[2][4]) {
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-      for (int g = 0; g < 4; ++g) m[i][g] = p2_load8(m_rsrc, moff[i], (j * 32 + 8 * g) * 2);
+      for (int g = 0; g < 4; ++g) m[i][g] = load8(m_rsrc, moff[i], (j * 32 + 8 * g) * 2);
   };
   int kt = 0;                     // current k-tile of the pass (chunk * 9 + tap)
   // One k-tile = tap TAP of the current chunk, in ring stage TAP % 3.  On entry fa[0] / fb hold its k-step 0.
@@ -382,7 +346,7 @@ __device__ __forceinline__ void p2_pass(const P2Params& p, const int pass, unsig
       // L2-resident weight stream) gets two k-tiles to arrive instead of one
       constexpr bool DMAP_PREV = !LASTC && TAP_ >= 1 && TAP_ <= 6;
       constexpr int MASK_FLY = (MASK_EARLY && LASTC && TAP_ >= 6) ? 8 : 0;      // (the mask loads of column tile 0: youngest in the queue)
-      __builtin_amdgcn_s_waitcnt(p2_wait((DMAW ? NBW : 0) + (DMAP ? 1 : 0) + (DMAP_PREV ? 1 : 0) + MASK_FLY));
+      __builtin_amdgcn_s_waitcnt(wait_vm((DMAW ? NBW : 0) + (DMAP ? 1 : 0) + (DMAP_PREV ? 1 : 0) + MASK_FLY));
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
       if constexpr (TAP_ == 8) {                              // next k-tile: tap 0 of the next chunk, the other patch buffer
@@ -430,7 +394,7 @@ __device__ __forceinline__ void p2_pass(const P2Params& p, const int pass, unsig
   // lower lane both halves of an even group and the upper lane both halves of the odd group next to it, and every lane stores 16
   // contiguous bytes (bf16: 8 columns; fp32: 2 x 4 columns).  No LDS staging, no wait on the stores.
   asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_waitcnt(p2_wait(63));
+  __builtin_amdgcn_s_waitcnt(wait_vm(63));
   __builtin_amdgcn_s_barrier();                // every wave is done with the patch buffers and the weight ring
   asm volatile("" ::: "memory");
   unsigned long long tl_e0 = 0, tl_pack = 0;
@@ -477,9 +441,9 @@ __device__ __forceinline__ void p2_pass(const P2Params& p, const int pass, unsig
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
           if (p.res_f32) {
-            rv[g] = p2_load16(r_rsrc, roff[i], (j * 32 + 8 * g) * 4);
+            rv[g] = load16(r_rsrc, roff[i], (j * 32 + 8 * g) * 4);
           } else {
-            const u32x2_t h = p2_load8(r_rsrc, roff[i], (j * 32 + 8 * g) * 2);
+            const u32x2 h = load8(r_rsrc, roff[i], (j * 32 + 8 * g) * 2);
             rv[g][0] = __builtin_bit_cast(float, h[0] << 16); rv[g][1] = __builtin_bit_cast(float, h[0] & 0xFFFF0000u);
             rv[g][2] = __builtin_bit_cast(float, h[1] << 16); rv[g][3] = __builtin_bit_cast(float, h[1] & 0xFFFF0000u);
           }
@@ -506,7 +470,7 @@ __device__ __forceinline__ void p2_pass(const P2Params& p, const int pass, unsig
         // out *= (mask > 0 ? 1 : mask_slope): the sign / zero test runs on the stored 16-bit patterns
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-          const u32x2_t m = mv[MASK_EARLY ? (j & 1) : 0][i][g];
+          const u32x2 m = mv[MASK_EARLY ? (j & 1) : 0][i][g];
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const unsigned w_ = m[e >> 1];
@@ -525,28 +489,26 @@ __device__ __forceinline__ void p2_pass(const P2Params& p, const int pass, unsig
       if (!p.out_f32) {
 #pragma unroll
         for (int gp = 0; gp < 2; ++gp) {
-          const u32x2_t X = __builtin_bit_cast(u32x2_t, __builtin_convertvector(vv[2 * gp], p2_bf16x4));
-          const u32x2_t Y = __builtin_bit_cast(u32x2_t, __builtin_convertvector(vv[2 * gp + 1], p2_bf16x4));
-          const u32x2_t s0 = p2_swap32(X[0], Y[0]), s1 = p2_swap32(X[1], Y[1]);
-          const u32x4_t o = {s0[0], s1[0], s0[1], s1[1]};
+          const u32x2 X = __builtin_bit_cast(u32x2, __builtin_convertvector(vv[2 * gp], p2_bf16x4));
+          const u32x2 Y = __builtin_bit_cast(u32x2, __builtin_convertvector(vv[2 * gp + 1], p2_bf16x4));
+          const u32x2 s0 = swap32(X[0], Y[0]), s1 = swap32(X[1], Y[1]);
+          const u32x4 o = {s0[0], s1[0], s0[1], s1[1]};
           const int gcol = 8 * (2 * gp + lhe);
-          p2_store16(__builtin_bit_cast(f32x4, o), o_rsrc,
-                     (!pok[i] || (tile0 + j) * 32 + gcol >= p.Cout) ? 0xFFFFFFF0u : (pbase + (unsigned)gcol) * 2u);
+          store16(o, o_rsrc, (!pok[i] || (tile0 + j) * 32 + gcol >= p.Cout) ? 0xFFFFFFF0u : (pbase + (unsigned)gcol) * 2u);
         }
       } else {
 #pragma unroll
         for (int gp = 0; gp < 2; ++gp) {
           const f32x4 xa = vv[2 * gp], xb = vv[2 * gp + 1];
-          const u32x2_t a0 = p2_swap32(p2_bits(xa[0]), p2_bits(xb[0]));
-          const u32x2_t a1 = p2_swap32(p2_bits(xa[1]), p2_bits(xb[1]));
-          const u32x2_t a2 = p2_swap32(p2_bits(xa[2]), p2_bits(xb[2]));
-          const u32x2_t a3 = p2_swap32(p2_bits(xa[3]), p2_bits(xb[3]));
-          const u32x4_t lo_ = {a0[0], a1[0], a2[0], a3[0]}, hi_ = {a0[1], a1[1], a2[1], a3[1]};
-          const f32x4 lo4 = __builtin_bit_cast(f32x4, lo_), hi4 = __builtin_bit_cast(f32x4, hi_);
+          const u32x2 a0 = swap32(bits(xa[0]), bits(xb[0]));
+          const u32x2 a1 = swap32(bits(xa[1]), bits(xb[1]));
+          const u32x2 a2 = swap32(bits(xa[2]), bits(xb[2]));
+          const u32x2 a3 = swap32(bits(xa[3]), bits(xb[3]));
+          const u32x4 lo_ = {a0[0], a1[0], a2[0], a3[0]}, hi_ = {a0[1], a1[1], a2[1], a3[1]};
           const int gcol = 8 * (2 * gp + lhe);
           const int colg = (tile0 + j) * 32 + gcol;
-          p2_store16(lo4, o_rsrc, (!pok[i] || colg >= p.Cout) ? 0xFFFFFFF0u : (pbase + (unsigned)gcol) * 4u);
-          p2_store16(hi4, o_rsrc, (!pok[i] || colg + 4 >= p.Cout) ? 0xFFFFFFF0u : (pbase + (unsigned)gcol + 4u) * 4u);
+          store16(lo_, o_rsrc, (!pok[i] || colg >= p.Cout) ? 0xFFFFFFF0u : (pbase + (unsigned)gcol) * 4u);
+          store16(hi_, o_rsrc, (!pok[i] || colg + 4 >= p.Cout) ? 0xFFFFFFF0u : (pbase + (unsigned)gcol + 4u) * 4u);
         }
       }
     }
@@ -595,7 +557,7 @@ __global__ __launch_bounds__(256, p2_blocks_per_cu(NTP)) void conv_p2_kernel(con
       p2_pass<NTP, EPI>(p, pass, smem, T, bid, lc, u == (int)blockIdx.x && pass == pa, pass == pa, lastp, nxt_pass, lastp ? TN : T);
     }
     if (p.tlog) {
-      __builtin_amdgcn_s_waitcnt(p2_wait(0));
+      __builtin_amdgcn_s_waitcnt(wait_vm(0));
       if (threadIdx.x == 0) p.tlog[(size_t)bid * 8 + 3] = wall_clock64();
     }
   }

@@ -1,5 +1,6 @@
 // Shared by the convolution kernels (conv_f32.hip: the generic implicit-GEMM engine; conv_patchw.hip: the wide
-// patch-mode kernel): launch parameters, element-type helpers, LDS-DMA primitives.
+// patch-mode kernel; conv_p2.hip / conv_s2.hip; the weight gradients of wgrad_lds_dma.h): launch parameters, element-type
+// helpers, LDS-DMA and raw-buffer primitives.
 #pragma once
 #include "hrv_common.h"
 
@@ -159,22 +160,45 @@ __device__ __forceinline__ void st1rt(float* base, size_t idx, float v, int is_f
   st1e<false>(base, idx, v);
 }
 
-// LDS-DMA primitives.  The buffer-resource type and builtins exist in the device pass only; the host pass
+// LDS-DMA and raw-buffer primitives.  The buffer-resource type and builtins exist in the device pass only; the host pass
 // (which still parses kernel bodies to emit launch stubs) sees inert stand-ins.
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 #if defined(__HIP_DEVICE_COMPILE__)
 typedef __amdgpu_buffer_rsrc_t rsrc_t;
 __device__ __forceinline__ rsrc_t make_rsrc(const void* base, unsigned bytes) {
   return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
 }
 // 16 bytes per lane: global[base + voff + soff] -> LDS[lds (wave-uniform) + 16*lane]; offsets past `bytes` store 0
-__device__ __forceinline__ void dma16(rsrc_t r, float* lds, unsigned voff, unsigned soff) {
+__device__ __forceinline__ void dma16(rsrc_t r, void* lds, unsigned voff, unsigned soff) {
   __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds, 16, voff, soff, 0, 0);
+}
+// 8 / 16 bytes per lane from / to global[base + voff + soff]; offsets past `bytes` load 0 / store nothing
+__device__ __forceinline__ void store16(u32x4 v, rsrc_t r, unsigned voff) { __builtin_amdgcn_raw_buffer_store_b128(v, r, (int)voff, 0, 0); }
+__device__ __forceinline__ u32x2 load8(rsrc_t r, unsigned voff, int soff) { return __builtin_amdgcn_raw_buffer_load_b64(r, (int)voff, soff, 0); }
+__device__ __forceinline__ f32x4 load16(rsrc_t r, unsigned voff, int soff) {
+  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, soff, 0));
+}
+// v_permlane32_swap: lanes 0..31 of the result pair hold (lo, lo of lane + 32), lanes 32..63 hold (hi of lane - 32, hi)
+__device__ __forceinline__ u32x2 swap32(unsigned lo, unsigned hi) {
+  const auto s = __builtin_amdgcn_permlane32_swap(lo, hi, false, false);
+  u32x2 r;
+  r[0] = s[0]; r[1] = s[1];
+  return r;
 }
 #else
 struct rsrc_t { int unused; };
 __device__ inline rsrc_t make_rsrc(const void*, unsigned) { return rsrc_t{0}; }
-__device__ inline void dma16(rsrc_t, float*, unsigned, unsigned) {}
+__device__ inline void dma16(rsrc_t, void*, unsigned, unsigned) {}
+__device__ inline void store16(u32x4, rsrc_t, unsigned) {}
+__device__ inline u32x2 load8(rsrc_t, unsigned, int) { return u32x2{0, 0}; }
+__device__ inline f32x4 load16(rsrc_t, unsigned, int) { return f32x4{0.f, 0.f, 0.f, 0.f}; }
+__device__ inline u32x2 swap32(unsigned a, unsigned b) { return u32x2{a, b}; }
 #endif
+// (by value: __builtin_bit_cast applied to a vector ELEMENT expression reads element 0 whatever the index)
+__device__ __forceinline__ unsigned bits(float f) { return __builtin_bit_cast(unsigned, f); }
+// s_waitcnt word: vmcnt(vm) lgkmcnt(0)
+constexpr int wait_vm(int vm) { return (vm & 15) | (7 << 4) | (0 << 8) | ((vm >> 4) << 14); }
 
 
 // conv_patchw.hip: 16x16-pixel patch tiles x up to 192 columns per block, one block per CU (tile_cfg 19)

@@ -29,31 +29,6 @@
 
 namespace hrv {
 
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef unsigned s2_u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned s2_u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void s2_store16(s2_u32x4 v, rsrc_t r, unsigned voff) { __builtin_amdgcn_raw_buffer_store_b128(v, r, (int)voff, 0, 0); }
-__device__ __forceinline__ s2_u32x2 s2_load8(rsrc_t r, unsigned voff, int soff) { return __builtin_amdgcn_raw_buffer_load_b64(r, (int)voff, soff, 0); }
-__device__ __forceinline__ f32x4 s2_load16(rsrc_t r, unsigned voff, int soff) {
-  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, soff, 0));
-}
-__device__ __forceinline__ s2_u32x2 s2_swap32(unsigned lo, unsigned hi) {
-  const auto s = __builtin_amdgcn_permlane32_swap(lo, hi, false, false);
-  s2_u32x2 r;
-  r[0] = s[0]; r[1] = s[1];
-  return r;
-}
-#else
-typedef unsigned s2_u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned s2_u32x4 __attribute__((ext_vector_type(4)));
-__device__ inline void s2_store16(s2_u32x4, rsrc_t, unsigned) {}
-__device__ inline s2_u32x2 s2_load8(rsrc_t, unsigned, int) { return s2_u32x2{0, 0}; }
-__device__ inline f32x4 s2_load16(rsrc_t, unsigned, int) { return f32x4{0.f, 0.f, 0.f, 0.f}; }
-__device__ inline s2_u32x2 s2_swap32(unsigned a, unsigned b) { return s2_u32x2{a, b}; }
-#endif
-// (by value: __builtin_bit_cast applied to a vector ELEMENT expression reads element 0 whatever the index, conv_p2.hip)
-__device__ __forceinline__ unsigned s2_bits(float f) { return __builtin_bit_cast(unsigned, f); }
-
 constexpr int S2_MAXP = 16;
 constexpr int S2_PW = 20;                                // patch pitch in cells (a multiple of 4: the swizzle keys on hx)
 constexpr int S2_PBUF = 23 * 1024;                       // 17 rows x 20 cells x 64 B = 21,760, DMA'd as 22 (+1 empty) pieces of 1 KB
@@ -197,8 +172,6 @@ __global__ __launch_bounds__(256) void s2_pack_multi_kernel(const S2PackMulti m)
 }
 
 // ------------------------------------------------------------------------------------------------ the kernel
-constexpr int s2_wait(int vm) { return (vm & 15) | (7 << 4) | (0 << 8) | ((vm >> 4) << 14); }   // vmcnt(vm) lgkmcnt(0)
-
 struct S2Tile { int n, y0, x0; };
 __device__ __forceinline__ S2Tile s2_tile(const S2Params& p, int bid) {
   const int tx = (p.Wt + 15) >> 4, ty = (p.Ht + 15) >> 4;
@@ -277,7 +250,7 @@ __device__ __forceinline__ void s2_pass(const S2Params& p, const int pass, unsig
   };
 
   // every wave is done with the previous (tile, pass): its bias sits in cbuf
-  __builtin_amdgcn_s_waitcnt(s2_wait(63));
+  __builtin_amdgcn_s_waitcnt(wait_vm(63));
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
   if (load_consts && tid < NTP * 32) cbuf[tid] = (p.bias && tile0 * 32 + tid < p.Cout) ? p.bias[tile0 * 32 + tid] : 0.f;
@@ -292,9 +265,9 @@ __device__ __forceinline__ void s2_pass(const S2Params& p, const int pass, unsig
 
   // The head (chunk 0, k-tiles 0 and 1) has landed.  Behind it in this wave's queue sit only the previous pass's epilogue
   // stores (they need not drain) -- unless this pass loaded constants, is the block's first, or the epilogue requested the head late
-  if (wait_all || load_consts || EPI != 0) __builtin_amdgcn_s_waitcnt(s2_wait(0));
-  else if (p.out_f32) __builtin_amdgcn_s_waitcnt(s2_wait(2 * NST));
-  else __builtin_amdgcn_s_waitcnt(s2_wait(NST));
+  if (wait_all || load_consts || EPI != 0) __builtin_amdgcn_s_waitcnt(wait_vm(0));
+  else if (p.out_f32) __builtin_amdgcn_s_waitcnt(wait_vm(2 * NST));
+  else __builtin_amdgcn_s_waitcnt(wait_vm(NST));
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
   // the accumulators start at the bias (cbuf: this pass's columns, zeros without a bias; published by the barrier above)
@@ -370,7 +343,7 @@ __device__ __forceinline__ void s2_pass(const S2Params& p, const int pass, unsig
       // k-tile kt + 1 must have landed.  In flight may stay what this wave requested BEHIND it: the previous tap's patch pieces,
       // this tap's k-tile kt + 2 and this tap's patch pieces.  At tap 3 nothing of the next chunk's patch is left in flight.
       constexpr int NP_PREV = (!LASTC && TAP_ >= 1 && TAP_ <= 2) ? NPT : 0;
-      __builtin_amdgcn_s_waitcnt(s2_wait((DMAW ? NBW : 0) + (DMAP ? NPT : 0) + NP_PREV));
+      __builtin_amdgcn_s_waitcnt(wait_vm((DMAW ? NBW : 0) + (DMAP ? NPT : 0) + NP_PREV));
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
       if constexpr (TAP_ == 3) {                              // next k-tile: tap 0 of the next chunk, the other patch buffer
@@ -409,7 +382,7 @@ __device__ __forceinline__ void s2_pass(const S2Params& p, const int pass, unsig
   // 8g .. 8g+3 and 8g+4 .. 8g+7 of ONE cell, v_permlane32_swap hands each lane 16 contiguous bytes.  A column tile's rows go to the
   // pixel of ITS phase (ostep 2).
   asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_waitcnt(s2_wait(63));
+  __builtin_amdgcn_s_waitcnt(wait_vm(63));
   __builtin_amdgcn_s_barrier();                // every wave is done with the patch buffers and the weight ring
   asm volatile("" ::: "memory");
   int lane_e = lane;
@@ -448,7 +421,7 @@ __device__ __forceinline__ void s2_pass(const S2Params& p, const int pass, unsig
       pix[i] = (unsigned)(py * p.Wo + px);
     }
   };
-  s2_u32x2 mv[2][4];
+  u32x2 mv[2][4];
   f32x4 rv[2][4];
   auto load_extra = [&](const int j) {
     int ch0;
@@ -462,9 +435,9 @@ __device__ __forceinline__ void s2_pass(const S2Params& p, const int pass, unsig
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
           if (p.res_f32) {
-            rv[i][g] = s2_load16(r_rsrc, roff, 8 * g * 4);
+            rv[i][g] = load16(r_rsrc, roff, 8 * g * 4);
           } else {
-            const s2_u32x2 h = s2_load8(r_rsrc, roff, 8 * g * 2);
+            const u32x2 h = load8(r_rsrc, roff, 8 * g * 2);
             rv[i][g][0] = __builtin_bit_cast(float, h[0] << 16); rv[i][g][1] = __builtin_bit_cast(float, h[0] & 0xFFFF0000u);
             rv[i][g][2] = __builtin_bit_cast(float, h[1] << 16); rv[i][g][3] = __builtin_bit_cast(float, h[1] & 0xFFFF0000u);
           }
@@ -473,7 +446,7 @@ __device__ __forceinline__ void s2_pass(const S2Params& p, const int pass, unsig
       if (has_mask) {
         const unsigned moff = pok[i] ? (pix[i] * (unsigned)p.mask_cs + (unsigned)(p.mask_co + ch0 + 4 * lhe)) * 2u : S2_OOB;
 #pragma unroll
-        for (int g = 0; g < 4; ++g) mv[i][g] = s2_load8(m_rsrc, moff, 8 * g * 2);
+        for (int g = 0; g < 4; ++g) mv[i][g] = load8(m_rsrc, moff, 8 * g * 2);
       }
     }
   };
@@ -517,7 +490,7 @@ __device__ __forceinline__ void s2_pass(const S2Params& p, const int pass, unsig
         // out *= (mask > 0 ? 1 : mask_slope): the sign / zero test runs on the stored 16-bit patterns
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-          const s2_u32x2 m = mv[i][g];
+          const u32x2 m = mv[i][g];
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const unsigned w_ = m[e >> 1];
@@ -541,26 +514,26 @@ __device__ __forceinline__ void s2_pass(const S2Params& p, const int pass, unsig
       if (!p.out_f32) {
 #pragma unroll
         for (int gp = 0; gp < 2; ++gp) {
-          const s2_u32x2 X = __builtin_bit_cast(s2_u32x2, __builtin_convertvector(vv[i][2 * gp], s2_bf16x4));
-          const s2_u32x2 Y = __builtin_bit_cast(s2_u32x2, __builtin_convertvector(vv[i][2 * gp + 1], s2_bf16x4));
-          const s2_u32x2 s0 = s2_swap32(X[0], Y[0]), s1 = s2_swap32(X[1], Y[1]);
-          const s2_u32x4 o = {s0[0], s1[0], s0[1], s1[1]};
+          const u32x2 X = __builtin_bit_cast(u32x2, __builtin_convertvector(vv[i][2 * gp], s2_bf16x4));
+          const u32x2 Y = __builtin_bit_cast(u32x2, __builtin_convertvector(vv[i][2 * gp + 1], s2_bf16x4));
+          const u32x2 s0 = swap32(X[0], Y[0]), s1 = swap32(X[1], Y[1]);
+          const u32x4 o = {s0[0], s1[0], s0[1], s1[1]};
           const int gcol = 8 * (2 * gp + lhe);
-          s2_store16(o, o_rsrc, (!pok[i] || (tile0 + j) * 32 + gcol >= p.Cout) ? 0xFFFFFFF0u : (pbase + (unsigned)gcol) * 2u);
+          store16(o, o_rsrc, (!pok[i] || (tile0 + j) * 32 + gcol >= p.Cout) ? 0xFFFFFFF0u : (pbase + (unsigned)gcol) * 2u);
         }
       } else {
 #pragma unroll
         for (int gp = 0; gp < 2; ++gp) {
           const f32x4 xa = vv[i][2 * gp], xb = vv[i][2 * gp + 1];
-          const s2_u32x2 a0 = s2_swap32(s2_bits(xa[0]), s2_bits(xb[0]));
-          const s2_u32x2 a1 = s2_swap32(s2_bits(xa[1]), s2_bits(xb[1]));
-          const s2_u32x2 a2 = s2_swap32(s2_bits(xa[2]), s2_bits(xb[2]));
-          const s2_u32x2 a3 = s2_swap32(s2_bits(xa[3]), s2_bits(xb[3]));
-          const s2_u32x4 lo_ = {a0[0], a1[0], a2[0], a3[0]}, hi_ = {a0[1], a1[1], a2[1], a3[1]};
+          const u32x2 a0 = swap32(bits(xa[0]), bits(xb[0]));
+          const u32x2 a1 = swap32(bits(xa[1]), bits(xb[1]));
+          const u32x2 a2 = swap32(bits(xa[2]), bits(xb[2]));
+          const u32x2 a3 = swap32(bits(xa[3]), bits(xb[3]));
+          const u32x4 lo_ = {a0[0], a1[0], a2[0], a3[0]}, hi_ = {a0[1], a1[1], a2[1], a3[1]};
           const int gcol = 8 * (2 * gp + lhe);
           const int colg = (tile0 + j) * 32 + gcol;
-          s2_store16(lo_, o_rsrc, (!pok[i] || colg >= p.Cout) ? 0xFFFFFFF0u : (pbase + (unsigned)gcol) * 4u);
-          s2_store16(hi_, o_rsrc, (!pok[i] || colg + 4 >= p.Cout) ? 0xFFFFFFF0u : (pbase + (unsigned)gcol + 4u) * 4u);
+          store16(lo_, o_rsrc, (!pok[i] || colg >= p.Cout) ? 0xFFFFFFF0u : (pbase + (unsigned)gcol) * 4u);
+          store16(hi_, o_rsrc, (!pok[i] || colg + 4 >= p.Cout) ? 0xFFFFFFF0u : (pbase + (unsigned)gcol + 4u) * 4u);
         }
       }
     }

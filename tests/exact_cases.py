@@ -411,6 +411,7 @@ WGRAD = [("class0", "conv_wgrad_tr_kernel[class 0]", 128, 160, 3, 1, 1, 2, 70, 7
          ("class7", "conv_wgrad_tr_kernel[class 7]", 256, 64, 3, 1, 1, 2, 70, 72, False, False, True),
          ("class8_2x2", "conv_wgrad_tr_kernel[class 8]", 48, 64, 2, 1, 1, 2, 70, 72, False, False, True),
          ("s2", "conv_wgrad_s2_kernel", 64, 128, 4, 2, 2, 2, 129, 131, False, False, True),
+         ("s2_c2", "conv_wgrad_s2_kernel", 128, 256, 4, 2, 2, 2, 129, 131, False, False, True),
          ("fallback_528", "conv_wgrad_kernel[bf16 stored]", 528, 64, 3, 1, 1, 2, 34, 36, False, True, True),
          ("fp32", "conv_wgrad_kernel[fp32]", 16, 24, 3, 1, 1, 2, 33, 47, False, True, False)]
 
