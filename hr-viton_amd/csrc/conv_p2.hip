@@ -19,17 +19,10 @@
 #include <type_traits>
 #include <utility>
 
-#include "conv_params.h"
+#include "patch_pass.h"
 
 namespace hrv {
 
-__device__ __forceinline__ f32x4 p2_acc4(const f32x16& a, int g) {
-  f32x4 r;
-  r[0] = a[4 * g]; r[1] = a[4 * g + 1]; r[2] = a[4 * g + 2]; r[3] = a[4 * g + 3];
-  return r;
-}
-
-constexpr int P2_MAXP = 16;
 constexpr int P2_PW = 20;                                // patch pitch in pixels (a multiple of 4: the swizzle keys on hx)
 constexpr int P2_PBUF = 23 * 1024;                       // 18 x 20 pixels x 64 B = 23,040, DMA'd as 23 pieces of 1 KB
 // LDS layout by pass width NTP (column tiles of 32): [ring: 3 stages of 32 k x 32 NTP columns][patch x 2][bias].  NTP 4: 72,192 B,
@@ -48,9 +41,9 @@ struct P2Params {
   int N, H, W;
   const void* wp; unsigned w_bytes;
   int npass;
-  int ntp[P2_MAXP];         // column tiles of 32 per pass (4; the last pass 1..3)
-  int tile0[P2_MAXP];
-  unsigned woff[P2_MAXP];
+  int ntp[PATCH_MAXP];         // column tiles of 32 per pass (4; the last pass 1..3)
+  int tile0[PATCH_MAXP];
+  unsigned woff[PATCH_MAXP];
   int nchunk;               // Cin / 32
   int m_tiles;
   int Cout;
@@ -64,13 +57,7 @@ struct P2Params {
   int pp;                   // one (tile, pass) per unit of work (see conv_p2_kernel)
 };
 
-struct P2Plan {
-  int npass, ntp[P2_MAXP], tile0[P2_MAXP];
-  unsigned woff[P2_MAXP];
-  long long bytes;
-};
-
-static bool p2_plan(int Cin, int Cout, P2Plan& pl) {
+static bool p2_plan(int Cin, int Cout, PatchPlan& pl) {
   memset(&pl, 0, sizeof(pl));
   // K runs over 32-channel chunks; a source whose width is 16 off a multiple of 32 (the generator's 144 / 272-channel block inputs)
   // ends with a half-empty chunk: its upper 16 channels arrive as zeros (out-of-range DMA offsets) against zero weights
@@ -81,7 +68,7 @@ static bool p2_plan(int Cin, int Cout, P2Plan& pl) {
   if (Cin < 1 || Cout < 1) return false;
   const int NT = (Cout + 31) / 32;
   const int n4 = NT / 4, rem = NT % 4;
-  if (n4 + (rem ? 1 : 0) > P2_MAXP) return false;
+  if (n4 + (rem ? 1 : 0) > PATCH_MAXP) return false;
   pl.npass = n4 + (rem ? 1 : 0);
   long long off = 0;
   int t0 = 0;
@@ -102,7 +89,7 @@ static bool p2_plan(int Cin, int Cout, P2Plan& pl) {
 //                          its input channels = columns), taps flipped
 // mode 2 (data gradient over a PAIR): w, w2 [Cp][Ccol][3][3]; k < Cp -> w, k >= Cp -> w2 ([dgamma | dbeta]), taps flipped
 struct P2PackParams {
-  P2Plan pl;
+  PatchPlan pl;
   int mode, Cin, Cout, Cp;
   const float* w;
   const float* w2;
@@ -148,25 +135,13 @@ __global__ __launch_bounds__(256) void p2_pack_kernel(const P2PackParams p) {
 }
 
 // ------------------------------------------------------------------------------------------------ the kernel
-struct P2Tile { int n, y0, x0; };
-__device__ __forceinline__ P2Tile p2_tile(const P2Params& p, int bid) {
-  const int tx = (p.W + 15) >> 4, ty = (p.H + 15) >> 4;
-  const int mt = xcd_remap(bid, p.m_tiles);
-  P2Tile t;
-  t.n = mt / (tx * ty);
-  const int rr = mt - t.n * (tx * ty);
-  t.y0 = (rr / tx) << 4;
-  t.x0 = (rr % tx) << 4;
-  return t;
-}
-
 typedef __bf16 p2_bf16x4 __attribute__((ext_vector_type(4)));
 
 // piece `pp` (0..22; 23 folds back: same bytes to the same place) of the 32-channel chunk `chunk` of the tile's halo patch
 // -> patch buffer `buf`.  16 halo pixels x 4 groups of 8 channels per piece (linear patch order, pitch 20); the 16-byte
 // groups of a pixel are XOR-swizzled by (hx >> 2) & 3 on the SOURCE side.  Out of the image / beyond pixel 360: zeros.
 template <int NTP>
-__device__ __forceinline__ void p2_patch_piece(const P2Params& p, unsigned char* const smem, const rsrc_t a_rsrc, const P2Tile T, const int chunk,
+__device__ __forceinline__ void p2_patch_piece(const P2Params& p, unsigned char* const smem, const rsrc_t a_rsrc, const PatchTile T, const int chunk,
                                                const int buf, int pp, const int lane) {
   pp = pp < 23 ? pp : 22;
   const int P = pp * 16 + (lane >> 2), g = lane & 3;
@@ -180,7 +155,7 @@ __device__ __forceinline__ void p2_patch_piece(const P2Params& p, unsigned char*
 
 // The head of a (tile, pass): chunk 0 of the patch -> buffer 0 (6 pieces per wave), k-tiles 0 / 1 -> ring stages 0 / 1.
 template <int NTP>
-__device__ __forceinline__ void p2_head(const P2Params& p, const int pass, unsigned char* const smem, const P2Tile T, const int wave,
+__device__ __forceinline__ void p2_head(const P2Params& p, const int pass, unsigned char* const smem, const PatchTile T, const int wave,
                                         const int lane) {
   constexpr int NPW = NTP * 2, NBW = (NPW + 3) / 4;
   const rsrc_t a_rsrc = make_rsrc(reinterpret_cast<const char*>(p.src) + (size_t)T.n * p.src_bytes, p.src_bytes);
@@ -201,9 +176,9 @@ __device__ __forceinline__ void p2_head(const P2Params& p, const int pass, unsig
 // EPI: what the epilogue can be asked for -- 0: bias + activation; 1: + mask; 2: mask and / or residual in any combination (the
 // lean instances keep the registers of the others' operands out of the allocation)
 template <int NTP, int EPI>
-__device__ __forceinline__ void p2_pass(const P2Params& p, const int pass, unsigned char* const smem, const P2Tile T, const int bid,
+__device__ __forceinline__ void p2_pass(const P2Params& p, unsigned char* const smem, const int pass, const PatchTile T, const int bid,
                                         const bool load_consts, const bool wait_all, const bool first, const bool last, const int nxt_pass,
-                                        const P2Tile NT_) {
+                                        const PatchTile NT_) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, lh = lane >> 5;
@@ -436,7 +411,7 @@ __device__ __forceinline__ void p2_pass(const P2Params& p, const int pass, unsig
     for (int i = 0; i < 2; ++i) {
       f32x4 vv[4], rv[4];
 #pragma unroll
-      for (int g = 0; g < 4; ++g) vv[g] = p2_acc4(acc[i][j], g);
+      for (int g = 0; g < 4; ++g) vv[g] = acc4(acc[i][j], g);
       if (has_res) {
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
@@ -525,42 +500,14 @@ template <int NTP, int EPI>
 __global__ __launch_bounds__(256, p2_blocks_per_cu(NTP)) void conv_p2_kernel(const P2Params p, const int pass0, const int pass1) {
   __shared__ __attribute__((aligned(1024))) unsigned char smem[p2_lds(NTP)];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-  // A unit of work = one tile with the launch's passes pass0 .. pass1 one after the other (the source patch of the later passes
-  // comes out of L2) -- or, p.pp (fewer tiles than resident blocks: the 64 x 48 / 32 x 24 levels), ONE (tile, pass): the passes
-  // of a tile run on different CUs at the same time
-  const int npg = pass1 - pass0;
-  const int units = p.pp ? p.m_tiles * npg : p.m_tiles;
-  auto unit_tile = [&](const int u) { return p.pp ? u / npg : u; };
-  auto unit_pass = [&](const int u) { return p.pp ? pass0 + u % npg : pass0; };
-  if ((int)blockIdx.x < units) p2_head<NTP>(p, unit_pass(blockIdx.x), smem, p2_tile(p, unit_tile(blockIdx.x)), wave, lane);
-  int c_pass = -1;
-#pragma unroll 1
-  for (int u = blockIdx.x; u < units; u += gridDim.x) {
-    const int bid = unit_tile(u);
-    if (p.tlog && threadIdx.x == 0) {
-      unsigned hw, xcc;
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-      p.tlog[(size_t)bid * 8 + 4] = ((unsigned long long)xcc << 32) | hw;
-      p.tlog[(size_t)bid * 8 + 5] = blockIdx.x;
-    }
-    const P2Tile T = p2_tile(p, bid);
-    const int nu = u + gridDim.x;
-    const P2Tile TN = p2_tile(p, unit_tile(nu < units ? nu : u));
-    const int pa = unit_pass(u), pb = p.pp ? pa + 1 : pass1;
-#pragma unroll 1
-    for (int pass = pa; pass < pb; ++pass) {
-      const bool lastp = pass == pb - 1;
-      const int nxt_pass = !lastp ? pass + 1 : (nu < units ? unit_pass(nu) : -1);
-      const bool lc = c_pass != pass;
-      c_pass = pass;
-      p2_pass<NTP, EPI>(p, pass, smem, T, bid, lc, u == (int)blockIdx.x && pass == pa, pass == pa, lastp, nxt_pass, lastp ? TN : T);
-    }
-    if (p.tlog) {
-      __builtin_amdgcn_s_waitcnt(wait_vm(0));
-      if (threadIdx.x == 0) p.tlog[(size_t)bid * 8 + 3] = wall_clock64();
-    }
-  }
+  // (p.pp: the 64 x 48 / 32 x 24 levels)
+#define P2_TILE(BID) patch_tile(BID, p.W, p.H, p.m_tiles)
+#define P2_HEAD(PASS, T) p2_head<NTP>(p, PASS, smem, T, wave, lane)
+#define P2_PASS(...) p2_pass<NTP, EPI>(p, smem, __VA_ARGS__)
+  PATCH_PASS_UNITS(p, pass0, pass1, P2_TILE, P2_HEAD, P2_PASS, p.tlog)
+#undef P2_TILE
+#undef P2_HEAD
+#undef P2_PASS
 }
 
 }  // namespace hrv
@@ -568,26 +515,19 @@ __global__ __launch_bounds__(256, p2_blocks_per_cu(NTP)) void conv_p2_kernel(con
 using namespace hrv;
 
 extern "C" int64_t hrv_conv_p2_packed_bytes(int32_t Cin, int32_t Cout) {
-  P2Plan pl;
+  PatchPlan pl;
   if (!p2_plan(Cin, Cout, pl)) return -1;
   return pl.bytes;
 }
 
 extern "C" int hrv_conv_p2_supported(int32_t Cin, int32_t Cout, int32_t N, int32_t H, int32_t W) {
-  P2Plan pl;
+  PatchPlan pl;
   if (!p2_plan(Cin, Cout, pl)) return 0;
-  const int64_t tiles = (int64_t)N * ((H + 15) / 16) * ((W + 15) / 16);
   // two blocks per CU; measured down to 1.5 tiles per CU (VGG19's 128 x 96 level at 8 images: 384 tiles, 908 -> 1050+ TF/s) the kernel
   // beats the generic tiles clearly; round 5 took the threshold to 0.75 tiles per CU (the generator's 128 x 96 level at 4 images: 192
   // tiles) on a same-box alternating A/B of the whole iteration -- 72.28 -> 71.96 ms, three rounds, every pair in favour
   // (profiles/r05_ab_p2_threshold.txt).  HRV_CONV_P2_MIN_TILES_X4: the threshold in quarter-tiles per CU
-  const char* e = hrv::env("HRV_CONV_P2_MIN_TILES_X4");      // (cached by hrv::env: no getenv here after the first call)
-  int q4 = e ? atoi(e) : 3;
-  if (q4 < 1) q4 = 3;
-  // (round 6: counted in UNITS of work -- a level with fewer tiles than resident blocks spreads the column passes of a tile over
-  //  the CUs, so what has to fill the chip is tiles x passes: the 64 x 48 level's 48 tiles x 4 passes of a 512-column layer)
-  const int64_t units = tiles < 2 * (int64_t)persistent_cus() ? tiles * pl.npass : tiles;
-  return 4 * units >= q4 * (int64_t)persistent_cus() ? 1 : 0;
+  return patch_units_fill(patch_tiles(N, H, W), pl.npass, "HRV_CONV_P2_MIN_TILES_X4", 3);
 }
 
 extern "C" int hrv_conv_p2_pack_dev(int32_t mode, const float* w, const float* w2, int32_t Cin, int32_t Cout, const float* sigma, float wscale,
@@ -606,7 +546,7 @@ extern "C" int hrv_conv_p2_pack_dev(int32_t mode, const float* w, const float* w
 
 extern "C" int hrv_conv_p2_bf16(const hrv_conv_p2_t* d, hrv_stream_t stream) {
   HRV_REQUIRE(d != nullptr, "conv_p2: null descriptor");
-  P2Plan pl;
+  PatchPlan pl;
   HRV_REQUIRE(p2_plan(d->Cin, d->Cout, pl), "conv_p2: unsupported shape (K %d, columns %d)", d->Cin, d->Cout);
   HRV_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && (int64_t)d->N * d->H * d->W < ((int64_t)1 << 31), "conv_p2: bad extent");
   HRV_REQUIRE(d->src && d->w_packed && d->out, "conv_p2: null pointer");
@@ -630,23 +570,19 @@ extern "C" int hrv_conv_p2_bf16(const hrv_conv_p2_t* d, hrv_stream_t stream) {
   p.src = d->src; p.src_cs = d->src_cstride; p.src_co = d->src_coff; p.Cin = d->Cin; p.src_bytes = (unsigned)sbytes;
   p.N = d->N; p.H = d->H; p.W = d->W;
   p.wp = d->w_packed; p.w_bytes = (unsigned)pl.bytes;
-  p.npass = pl.npass; p.nchunk = (d->Cin + 31) / 32;
-  for (int i = 0; i < pl.npass; ++i) { p.ntp[i] = pl.ntp[i]; p.tile0[i] = pl.tile0[i]; p.woff[i] = pl.woff[i]; }
-  p.m_tiles = d->N * ((d->H + 15) / 16) * ((d->W + 15) / 16);
+  patch_plan_copy(p, pl);
+  p.nchunk = (d->Cin + 31) / 32;
+  p.m_tiles = (int)patch_tiles(d->N, d->H, d->W);
   p.Cout = d->Cout;
   p.bias = d->bias; p.act = d->act; p.slope = d->act_slope;
   p.res = d->residual; p.res_cs = d->res_cstride; p.res_co = d->res_coff; p.res_f32 = d->res_f32; p.res_after = d->res_after_mask;
   p.mask = d->mask; p.mask_cs = d->mask_cstride; p.mask_co = d->mask_coff; p.mask_slope = d->mask_slope;
   p.out = d->out; p.out_cs = d->out_cstride; p.out_co = d->out_coff; p.out_f32 = d->out_f32;
   p.tlog = diag_tlog(p.m_tiles);
-  p.pp = p.m_tiles < 2 * persistent_cus() ? 1 : 0;
+  p.pp = patch_pp(p.m_tiles) ? 1 : 0;
   if (p.pp) p.tlog = nullptr;          // (the timeline's slots are per tile)
-  for (int a = 0; a < pl.npass;) {
-    int b = a;
-    while (b < pl.npass && pl.ntp[b] == pl.ntp[a]) ++b;
-    const long long units = p.pp ? (long long)p.m_tiles * (b - a) : p.m_tiles;
-    const int cap = p2_blocks_per_cu(pl.ntp[a]) * persistent_cus();      // resident blocks: three per CU for single-tile passes
-    const int grid = units < cap ? (int)units : cap;
+  // (resident blocks: three per CU for single-tile passes)
+  patch_pass_groups(pl, p.m_tiles, p.pp != 0, p2_blocks_per_cu, [&](const int a, const int b, const int grid) {
     const dim3 g3(grid), b3(256);
     const hipStream_t st = (hipStream_t)stream;
     const int epi = p.res ? 2 : (p.mask ? 1 : 0);
@@ -661,7 +597,6 @@ extern "C" int hrv_conv_p2_bf16(const hrv_conv_p2_t* d, hrv_stream_t stream) {
     else if (pl.ntp[a] == 2) P2_LAUNCH(2)
     else P2_LAUNCH(1)
 #undef P2_LAUNCH
-    a = b;
-  }
+  });
   return check_launch("conv_p2_kernel");
 }

@@ -1,5 +1,5 @@
 // Shared by the convolution kernels (conv_f32.hip: the generic implicit-GEMM engine; conv_patchw.hip: the wide
-// patch-mode kernel; conv_p2.hip / conv_s2.hip; the weight gradients of wgrad_lds_dma.h): launch parameters, element-type
+// patch-mode kernel; the patch-pass kernels of patch_pass.h; the weight gradients of wgrad_lds_dma.h): launch parameters, element-type
 // helpers, LDS-DMA and raw-buffer primitives.
 #pragma once
 #include "hrv_common.h"
@@ -175,6 +175,7 @@ __device__ __forceinline__ void dma16(rsrc_t r, void* lds, unsigned voff, unsign
 }
 // 8 / 16 bytes per lane from / to global[base + voff + soff]; offsets past `bytes` load 0 / store nothing
 __device__ __forceinline__ void store16(u32x4 v, rsrc_t r, unsigned voff) { __builtin_amdgcn_raw_buffer_store_b128(v, r, (int)voff, 0, 0); }
+__device__ __forceinline__ void store16(f32x4 v, rsrc_t r, unsigned voff) { store16(__builtin_bit_cast(u32x4, v), r, voff); }
 __device__ __forceinline__ u32x2 load8(rsrc_t r, unsigned voff, int soff) { return __builtin_amdgcn_raw_buffer_load_b64(r, (int)voff, soff, 0); }
 __device__ __forceinline__ f32x4 load16(rsrc_t r, unsigned voff, int soff) {
   return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, soff, 0));
@@ -191,13 +192,14 @@ struct rsrc_t { int unused; };
 __device__ inline rsrc_t make_rsrc(const void*, unsigned) { return rsrc_t{0}; }
 __device__ inline void dma16(rsrc_t, void*, unsigned, unsigned) {}
 __device__ inline void store16(u32x4, rsrc_t, unsigned) {}
+__device__ inline void store16(f32x4, rsrc_t, unsigned) {}
 __device__ inline u32x2 load8(rsrc_t, unsigned, int) { return u32x2{0, 0}; }
 __device__ inline f32x4 load16(rsrc_t, unsigned, int) { return f32x4{0.f, 0.f, 0.f, 0.f}; }
 __device__ inline u32x2 swap32(unsigned a, unsigned b) { return u32x2{a, b}; }
 #endif
 // (by value: __builtin_bit_cast applied to a vector ELEMENT expression reads element 0 whatever the index)
 __device__ __forceinline__ unsigned bits(float f) { return __builtin_bit_cast(unsigned, f); }
-// s_waitcnt word: vmcnt(vm) lgkmcnt(0)
+// s_waitcnt word: vmcnt(vm) lgkmcnt(0)   (gfx9 encoding: vmcnt[3:0] bits 3:0, expcnt bits 6:4, lgkmcnt bits 11:8, vmcnt[5:4] bits 15:14)
 constexpr int wait_vm(int vm) { return (vm & 15) | (7 << 4) | (0 << 8) | ((vm >> 4) << 14); }
 
 

@@ -25,11 +25,10 @@
 #include <type_traits>
 #include <utility>
 
-#include "conv_params.h"
+#include "patch_pass.h"
 
 namespace hrv {
 
-constexpr int S2_MAXP = 16;
 constexpr int S2_PW = 20;                                // patch pitch in cells (a multiple of 4: the swizzle keys on hx)
 constexpr int S2_PBUF = 23 * 1024;                       // 17 rows x 20 cells x 64 B = 21,760, DMA'd as 22 (+1 empty) pieces of 1 KB
 constexpr int s2_sb(int ntp) { return ntp * 2048; }                                      // ring stage
@@ -47,8 +46,8 @@ struct S2Params {
   int N, Ht, Wt;            // tile grid extent in cells
   const void* wp; unsigned w_bytes;
   int npass;
-  int ntp[S2_MAXP], tile0[S2_MAXP];
-  unsigned woff[S2_MAXP];
+  int ntp[PATCH_MAXP], tile0[PATCH_MAXP];
+  unsigned woff[PATCH_MAXP];
   int m_tiles;
   int Cout;                 // columns
   const float* bias;
@@ -62,21 +61,14 @@ struct S2Params {
   int pp;                   // one (tile, pass) per unit of work
 };
 
-struct S2Plan {
-  int npass, ntp[S2_MAXP], tile0[S2_MAXP];
-  unsigned woff[S2_MAXP];
-  int nchunk;
-  long long bytes;
-};
-
 static int s2_chunks(int mode, int K) { return (mode == 0 ? 4 : 1) * ((K + 31) / 32); }
 
-static bool s2_plan(int mode, int K, int cols, S2Plan& pl) {
+static bool s2_plan(int mode, int K, int cols, PatchPlan& pl) {
   memset(&pl, 0, sizeof(pl));
   // columns in passes of 4 column tiles (128) and at most one of 2 (64): the PatchGAN's 64 / 128 / 256 / 512-column layers
   if (mode < 0 || mode > 2 || K < 1 || cols < 64 || cols % 64 != 0 || K % 8 != 0) return false;
   const int NT = cols / 32, n4 = NT / 4, rem = NT % 4;
-  if (n4 + (rem ? 1 : 0) > S2_MAXP) return false;
+  if (n4 + (rem ? 1 : 0) > PATCH_MAXP) return false;
   pl.npass = n4 + (rem ? 1 : 0);
   pl.nchunk = s2_chunks(mode, K);
   long long off = 0;
@@ -98,7 +90,7 @@ static bool s2_plan(int mode, int K, int cols, S2Plan& pl) {
 //         patch tap (a, b) <-> t = 1 - a: kh = 2 (1-a) + dy, kw = 2 (1-b) + dx
 // mode 2: w = [cols][K][2][2]
 struct S2PackParams {
-  S2Plan pl;
+  PatchPlan pl;
   int mode, K, cols, Cph;
   int split3;             // modes 0 / 2: K = 3 K0 over a source [hi | lo | hi]; weight thirds [hi(w) | hi(w) | w - hi(w)] of the K0-channel w
   const float* w;
@@ -172,25 +164,13 @@ __global__ __launch_bounds__(256) void s2_pack_multi_kernel(const S2PackMulti m)
 }
 
 // ------------------------------------------------------------------------------------------------ the kernel
-struct S2Tile { int n, y0, x0; };
-__device__ __forceinline__ S2Tile s2_tile(const S2Params& p, int bid) {
-  const int tx = (p.Wt + 15) >> 4, ty = (p.Ht + 15) >> 4;
-  const int mt = xcd_remap(bid, p.m_tiles);
-  S2Tile t;
-  t.n = mt / (tx * ty);
-  const int rr = mt - t.n * (tx * ty);
-  t.y0 = (rr / tx) << 4;
-  t.x0 = (rr % tx) << 4;
-  return t;
-}
-
 typedef __bf16 s2_bf16x4 __attribute__((ext_vector_type(4)));
 
 // piece `pp` (0..21; beyond: an empty piece) of chunk (sub-pixel `sub`, channels 32 cc ..) of the tile's halo patch -> patch buffer
 // `buf`.  16 cells x 4 groups of 8 channels per piece (linear patch order, pitch 20); the 16-byte groups of a cell are XOR-swizzled
 // by (hx >> 2) & 3 on the SOURCE side.  Outside the source / beyond its channels / row or column 17+: zeros.
 template <int NTP>
-__device__ __forceinline__ void s2_patch_piece(const S2Params& p, unsigned char* const smem, const rsrc_t a_rsrc, const S2Tile T, const int sub,
+__device__ __forceinline__ void s2_patch_piece(const S2Params& p, unsigned char* const smem, const rsrc_t a_rsrc, const PatchTile T, const int sub,
                                                const int cc, const int buf, int pp, const int lane) {
   pp = pp < 23 ? pp : 22;
   const int P = pp * 16 + (lane >> 2), g = lane & 3;
@@ -204,7 +184,7 @@ __device__ __forceinline__ void s2_patch_piece(const S2Params& p, unsigned char*
 
 // The head of a (tile, pass): chunk 0 of the patch -> buffer 0 (6 pieces per wave), k-tiles 0 / 1 -> ring stages 0 / 1.
 template <int NTP>
-__device__ __forceinline__ void s2_head(const S2Params& p, const int pass, unsigned char* const smem, const S2Tile T, const int wave,
+__device__ __forceinline__ void s2_head(const S2Params& p, const int pass, unsigned char* const smem, const PatchTile T, const int wave,
                                         const int lane) {
   constexpr int NPW = NTP * 2, NBW = (NPW + 3) / 4;
   const rsrc_t a_rsrc = make_rsrc(reinterpret_cast<const char*>(p.src) + (size_t)T.n * p.src_bytes, p.src_bytes);
@@ -224,8 +204,8 @@ __device__ __forceinline__ void s2_head(const S2Params& p, const int pass, unsig
 
 // EPI 0: bias + activation; 2: + residual and / or mask (their registers stay out of the lean instance's allocation)
 template <int NTP, int EPI>
-__device__ __forceinline__ void s2_pass(const S2Params& p, const int pass, unsigned char* const smem, const S2Tile T, const bool load_consts,
-                                        const bool wait_all, const int nxt_pass, const S2Tile NT_) {
+__device__ __forceinline__ void s2_pass(const S2Params& p, unsigned char* const smem, const int pass, const PatchTile T, const bool load_consts,
+                                        const bool wait_all, const int nxt_pass, const PatchTile NT_) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, lh = lane >> 5;
@@ -544,29 +524,13 @@ template <int NTP, int EPI>
 __global__ __launch_bounds__(256, 2) void conv_s2_kernel(const S2Params p, const int pass0, const int pass1) {
   __shared__ __attribute__((aligned(1024))) unsigned char smem[s2_lds(NTP)];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-  // A unit of work = one tile with the launch's passes pass0 .. pass1 one after the other (the source patch of the later passes
-  // comes out of L2) -- or, p.pp (fewer tiles than resident blocks), ONE (tile, pass)
-  const int npg = pass1 - pass0;
-  const int units = p.pp ? p.m_tiles * npg : p.m_tiles;
-  auto unit_tile = [&](const int u) { return p.pp ? u / npg : u; };
-  auto unit_pass = [&](const int u) { return p.pp ? pass0 + u % npg : pass0; };
-  if ((int)blockIdx.x < units) s2_head<NTP>(p, unit_pass(blockIdx.x), smem, s2_tile(p, unit_tile(blockIdx.x)), wave, lane);
-  int c_pass = -1;
-#pragma unroll 1
-  for (int u = blockIdx.x; u < units; u += gridDim.x) {
-    const S2Tile T = s2_tile(p, unit_tile(u));
-    const int nu = u + gridDim.x;
-    const S2Tile TN = s2_tile(p, unit_tile(nu < units ? nu : u));
-    const int pa = unit_pass(u), pb = p.pp ? pa + 1 : pass1;
-#pragma unroll 1
-    for (int pass = pa; pass < pb; ++pass) {
-      const bool lastp = pass == pb - 1;
-      const int nxt_pass = !lastp ? pass + 1 : (nu < units ? unit_pass(nu) : -1);
-      const bool lc = c_pass != pass;
-      c_pass = pass;
-      s2_pass<NTP, EPI>(p, pass, smem, T, lc, u == (int)blockIdx.x && pass == pa, nxt_pass, lastp ? TN : T);
-    }
-  }
+#define S2_TILE(BID) patch_tile(BID, p.Wt, p.Ht, p.m_tiles)
+#define S2_HEAD(PASS, T) s2_head<NTP>(p, PASS, smem, T, wave, lane)
+#define S2_PASS(PASS, T, BID, STALE, BLOCK_FIRST, FIRST, LAST, NXT_PASS, NT_) s2_pass<NTP, EPI>(p, smem, PASS, T, STALE, BLOCK_FIRST, NXT_PASS, NT_)
+  PATCH_PASS_UNITS(p, pass0, pass1, S2_TILE, S2_HEAD, S2_PASS, (unsigned long long*)nullptr)
+#undef S2_TILE
+#undef S2_HEAD
+#undef S2_PASS
 }
 
 }  // namespace hrv
@@ -574,7 +538,7 @@ __global__ __launch_bounds__(256, 2) void conv_s2_kernel(const S2Params p, const
 using namespace hrv;
 
 extern "C" int64_t hrv_conv_s2_packed_bytes(int32_t mode, int32_t K, int32_t cols) {
-  S2Plan pl;
+  PatchPlan pl;
   if (!s2_plan(mode, K, cols, pl)) return -1;
   return pl.bytes;
 }
@@ -586,18 +550,13 @@ static void s2_grid(int mode, int Ho, int Wo, int& Ht, int& Wt) {
 }
 
 extern "C" int hrv_conv_s2_supported(int32_t mode, int32_t K, int32_t cols, int32_t Cph, int32_t N, int32_t Ho, int32_t Wo) {
-  S2Plan pl;
+  PatchPlan pl;
   if (!s2_plan(mode, K, cols, pl)) return 0;
   if (mode == 0 && K % 32 != 0) return 0;                                  // a chunk lies in one sub-pixel
   if (mode == 1 && (Cph < 32 || Cph % 32 != 0 || cols != 4 * Cph)) return 0;      // a column tile lies in one phase
   int Ht, Wt;
   s2_grid(mode, Ho, Wo, Ht, Wt);
-  const int64_t tiles = (int64_t)N * ((Ht + 15) / 16) * ((Wt + 15) / 16);
-  const char* e = hrv::env("HRV_CONV_S2_MIN_TILES_X4");
-  int q4 = e ? atoi(e) : 3;
-  if (q4 < 1) q4 = 3;
-  const int64_t units = tiles < 2 * (int64_t)persistent_cus() ? tiles * pl.npass : tiles;
-  return 4 * units >= q4 * (int64_t)persistent_cus() ? 1 : 0;
+  return patch_units_fill(patch_tiles(N, Ht, Wt), pl.npass, "HRV_CONV_S2_MIN_TILES_X4", 3);
 }
 
 extern "C" int hrv_conv_s2_pack_dev(int32_t mode_flags, const float* w, int32_t K, int32_t cols, int32_t Cph, const float* sigma, float wscale,
@@ -636,7 +595,7 @@ extern "C" int hrv_conv_s2_pack_multi_dev(int32_t n, const hrv_s2_pack_job_t* jo
 
 extern "C" int hrv_conv_s2_bf16(const hrv_conv_s2_t* d, hrv_stream_t stream) {
   HRV_REQUIRE(d != nullptr, "conv_s2: null descriptor");
-  S2Plan pl;
+  PatchPlan pl;
   HRV_REQUIRE(s2_plan(d->mode, d->K, d->cols, pl), "conv_s2: unsupported shape (mode %d, K %d, columns %d)", d->mode, d->K, d->cols);
   HRV_REQUIRE(d->mode != 0 || d->K % 32 == 0, "conv_s2: forward K must be a multiple of 32 (got %d)", d->K);
   HRV_REQUIRE(d->mode != 1 || (d->Cph >= 32 && d->Cph % 32 == 0 && d->cols == 4 * d->Cph), "conv_s2: data gradient columns = 4 x Cph");
@@ -671,9 +630,8 @@ extern "C" int hrv_conv_s2_bf16(const hrv_conv_s2_t* d, hrv_stream_t stream) {
   p.N = d->N;
   s2_grid(d->mode, d->Ho, d->Wo, p.Ht, p.Wt);
   p.wp = d->w_packed; p.w_bytes = (unsigned)pl.bytes;
-  p.npass = pl.npass;
-  for (int i = 0; i < pl.npass; ++i) { p.ntp[i] = pl.ntp[i]; p.tile0[i] = pl.tile0[i]; p.woff[i] = pl.woff[i]; }
-  p.m_tiles = d->N * ((p.Ht + 15) / 16) * ((p.Wt + 15) / 16);
+  patch_plan_copy(p, pl);
+  p.m_tiles = (int)patch_tiles(d->N, p.Ht, p.Wt);
   p.Cout = d->cols;
   p.bias = d->bias;
   p.ostep = d->mode == 1 ? 2 : 1;
@@ -683,13 +641,8 @@ extern "C" int hrv_conv_s2_bf16(const hrv_conv_s2_t* d, hrv_stream_t stream) {
   p.res = d->residual; p.res_cs = d->res_cstride; p.res_co = d->res_coff; p.res_f32 = d->res_f32;
   p.act = d->act; p.slope = d->act_slope;
   p.mask = d->mask; p.mask_cs = d->mask_cstride; p.mask_co = d->mask_coff; p.mask_slope = d->mask_slope;
-  p.pp = p.m_tiles < 2 * persistent_cus() ? 1 : 0;
-  for (int a = 0; a < pl.npass;) {
-    int b = a;
-    while (b < pl.npass && pl.ntp[b] == pl.ntp[a]) ++b;
-    const long long units = p.pp ? (long long)p.m_tiles * (b - a) : p.m_tiles;
-    const int cap = 2 * persistent_cus();
-    const int grid = units < cap ? (int)units : cap;
+  p.pp = patch_pp(p.m_tiles) ? 1 : 0;
+  patch_pass_groups(pl, p.m_tiles, p.pp != 0, [](int) { return 2; }, [&](const int a, const int b, const int grid) {
     const dim3 g3(grid), b3(256);
     const hipStream_t st = (hipStream_t)stream;
     const bool lean = !p.res && !p.mask;
@@ -700,8 +653,7 @@ extern "C" int hrv_conv_s2_bf16(const hrv_conv_s2_t* d, hrv_stream_t stream) {
       if (lean) hipLaunchKernelGGL((conv_s2_kernel<2, 0>), g3, b3, 0, st, p, a, b);
       else hipLaunchKernelGGL((conv_s2_kernel<2, 2>), g3, b3, 0, st, p, a, b);
     }
-    a = b;
-  }
+  });
   return check_launch("conv_s2_kernel");
 }
 

@@ -33,26 +33,10 @@
 #include <type_traits>
 #include <utility>
 
-#include "conv_params.h"
+#include "patch_pass.h"
 
 namespace hrv {
 
-#if defined(__HIP_DEVICE_COMPILE__)
-__device__ __forceinline__ void gf_store16(f32x4 v, rsrc_t r, unsigned voff) {
-  typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), r, (int)voff, 0, 0);
-}
-#else
-__device__ inline void gf_store16(f32x4, rsrc_t, unsigned) {}
-#endif
-
-__device__ __forceinline__ f32x4 gf_acc4(const f32x16& a, int g) {
-  f32x4 r;
-  r[0] = a[4 * g]; r[1] = a[4 * g + 1]; r[2] = a[4 * g + 2]; r[3] = a[4 * g + 3];
-  return r;
-}
-
-constexpr int GF_MAXP = 16;
 constexpr int GF_SB = 10240;                            // ring stage: 32 k x 160 columns = one conv_shared half (80 k x 64 columns)
 constexpr int GF_SEG_OFF = 3 * GF_SB;                   // 30,720
 constexpr int GF_SEG_B = 7168;                          // 20 x 20 label pixels x 16 B = 6,400, DMA'd as 7 x 1 KB
@@ -74,9 +58,9 @@ struct GfParams {
   int N, H, W;
   const void* wp; unsigned w_bytes;
   int npass;
-  int ntp[GF_MAXP];         // column tiles of 32 per pass (2, 4 or 5)
-  int tile0[GF_MAXP];       // first column tile of the pass
-  unsigned woff[GF_MAXP];   // byte offset of the pass's k-tile stream in the packed weights
+  int ntp[PATCH_MAXP];         // column tiles of 32 per pass (2, 4 or 5)
+  int tile0[PATCH_MAXP];       // first column tile of the pass
+  unsigned woff[PATCH_MAXP];   // byte offset of the pass's k-tile stream in the packed weights
   int m_tiles;
   const float* sx; int sx_cs, sx_co, sx_f32, sC;
   // x = cat(nearest_up2(lo), hi), never materialised (sx_up_c > 0, fp32): channels [0, sx_up_c) from sx = lo [N][H/2][W/2][sx_cs]
@@ -91,15 +75,9 @@ struct GfParams {
   int pp;                   // one (tile, pass) per unit of work (see spade_fused_kernel)
 };
 
-struct GfPlan {
-  int npass, ntp[GF_MAXP], tile0[GF_MAXP];
-  unsigned woff[GF_MAXP];
-  long long bytes;
-};
-
 // columns = (gamma32 | beta32) pairs (+ one 16|16 tail tile) of C norm channels; passes of 4 column tiles, then one of 2,
 // then (16-channel tail) one of 5 = two pairs + the tail
-static bool gf_plan(int C, GfPlan& pl) {
+static bool gf_plan(int C, PatchPlan& pl) {
   memset(&pl, 0, sizeof(pl));
   if (C < 32 || C % 16 != 0) return false;
   const int NT = 2 * (C / 32) + (C % 32 ? 1 : 0);
@@ -108,7 +86,7 @@ static bool gf_plan(int C, GfPlan& pl) {
   if (rest < 0) return false;
   const int n2 = (rest % 4 == 2) ? 1 : 0;
   const int n4 = (rest - 2 * n2) / 4;
-  if (n4 + n2 + n5 > GF_MAXP || n4 + n2 + n5 < 1) return false;
+  if (n4 + n2 + n5 > PATCH_MAXP || n4 + n2 + n5 < 1) return false;
   pl.npass = n4 + n2 + n5;
   long long off = GF_HDR_B;
   int t0 = 0;
@@ -125,7 +103,7 @@ static bool gf_plan(int C, GfPlan& pl) {
 
 // ------------------------------------------------------------------------------------------------ weight packer
 struct GfPackParams {
-  GfPlan pl;
+  PatchPlan pl;
   int C, label_nc;
   const float* wsh;   // conv_shared.weight [128][label_nc][3][3]
   const float* bsh;   // conv_shared.bias [128]
@@ -200,21 +178,6 @@ __global__ __launch_bounds__(256) void gf_pack_kernel(const GfPackParams p) {
 }
 
 // ------------------------------------------------------------------------------------------------ the kernel
-// s_waitcnt immediates (gfx9 encoding: vmcnt[3:0] bits 3:0, expcnt bits 6:4, lgkmcnt bits 11:8, vmcnt[5:4] bits 15:14)
-constexpr int gf_wait(int vm) { return (vm & 15) | (7 << 4) | (0 << 8) | ((vm >> 4) << 14); }   // vmcnt(vm) lgkmcnt(0)
-
-struct GfTile { int n, y0, x0; };
-__device__ __forceinline__ GfTile gf_tile(const GfParams& p, int bid) {
-  const int tx = (p.W + 15) >> 4, ty = (p.H + 15) >> 4;
-  const int mt = xcd_remap(bid, p.m_tiles);
-  GfTile t;
-  t.n = mt / (tx * ty);
-  const int rr = mt - t.n * (tx * ty);
-  t.y0 = (rr / tx) << 4;
-  t.x0 = (rr % tx) << 4;
-  return t;
-}
-
 typedef __bf16 gf_bf16x4 __attribute__((ext_vector_type(4)));
 
 // The head of a (tile, pass): what its first barrier waits for -- the label patch (first pass of a tile), the conv_shared
@@ -222,7 +185,7 @@ typedef __bf16 gf_bf16x4 __attribute__((ext_vector_type(4)));
 // loop (ring and label patch are free then), so the loads fly under that pass's epilogue and are OLDER than its stores:
 // the counted wait at the top of this pass does not wait for the stores to drain.
 template <int NTP>
-__device__ __forceinline__ void gf_head(const GfParams& p, const int pass, unsigned char* const smem, const GfTile T, const bool load_seg,
+__device__ __forceinline__ void gf_head(const GfParams& p, const int pass, unsigned char* const smem, const PatchTile T, const bool load_seg,
                                         const int wave, const int lane) {
   constexpr int NPW = NTP * 2, NBW = (NPW + 3) / 4;
   unsigned char* const ring = smem;
@@ -264,9 +227,9 @@ __device__ __forceinline__ void gf_head(const GfParams& p, const int pass, unsig
 // another (image, pass).  ``wait_all``: nothing of a previous pass is in flight behind the head (first pass of the block).
 // ``nxt_*``: the (tile, pass) whose head this pass issues after its main loop (nxt_pass < 0: none).
 template <int NTP>
-__device__ __forceinline__ void gf_pass(const GfParams& p, const int pass, unsigned char* const smem, const GfTile T, const int bid,
+__device__ __forceinline__ void gf_pass(const GfParams& p, unsigned char* const smem, const int pass, const PatchTile T, const int bid,
                                         const bool load_consts, const bool wait_all, const bool save_actv, const bool first, const bool last,
-                                        const int nxt_pass, const GfTile NT_, const bool nxt_seg) {
+                                        const int nxt_pass, const PatchTile NT_, const bool nxt_seg) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, lh = lane >> 5;
@@ -306,7 +269,7 @@ __device__ __forceinline__ void gf_pass(const GfParams& p, const int pass, unsig
   };
 
   // every wave is done with the previous (tile, pass): its epilogue's staging scratch lives in the patch, its constants in cbuf
-  __builtin_amdgcn_s_waitcnt(gf_wait(63));
+  __builtin_amdgcn_s_waitcnt(wait_vm(63));
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
   if (p.tlog && tid == 0 && first) p.tlog[(size_t)bid * 8 + 0] = wall_clock64();
@@ -401,7 +364,7 @@ __device__ __forceinline__ void gf_pass(const GfParams& p, const int pass, unsig
         unsigned char* const dst = patch + P * 128 + lh * 8;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-          f32x4 v0 = gf_acc4(c0, g), v1 = gf_acc4(c1, g);
+          f32x4 v0 = acc4(c0, g), v1 = acc4(c1, g);
 #pragma unroll
           for (int e = 0; e < 4; ++e) { v0[e] = fmaxf(v0[e], 0.f) * keep; v1[e] = fmaxf(v1[e], 0.f) * keep; }
           *reinterpret_cast<gf_bf16x4*>(dst + ((((unsigned)g) ^ sw) << 4)) = __builtin_convertvector(v0, gf_bf16x4);
@@ -425,22 +388,22 @@ __device__ __forceinline__ void gf_pass(const GfParams& p, const int pass, unsig
       const f32x4 v = *reinterpret_cast<const f32x4*>(patch + (hy * GF_PP + hx) * 128 + ((((unsigned)g) ^ ((unsigned)(hx >> 1) & 7u)) << 4));
       const int y = pt_y0 + hy - 1, x = pt_x0 + hx - 1;
       const unsigned off = (y < p.H && x < p.W) ? (unsigned)((y * p.W + x) * p.actv_cs + p.actv_co + half * 64 + g * 8) * 2u : 0xFFFFFFF0u;
-      gf_store16(v, a_rsrc, off);
+      store16(v, a_rsrc, off);
     }
   };
 
   // The head (label patch, items 0 and 1) has landed.  Behind it in this wave's queue sit only the previous pass's epilogue
   // stores (NST of them: they need not drain) -- unless this pass loaded constants or is the block's first
-  if (wait_all || load_consts) __builtin_amdgcn_s_waitcnt(gf_wait(0));
-  else if (p.g1p) __builtin_amdgcn_s_waitcnt(gf_wait(NST2));
-  else __builtin_amdgcn_s_waitcnt(gf_wait(NST1));
+  if (wait_all || load_consts) __builtin_amdgcn_s_waitcnt(wait_vm(0));
+  else if (p.g1p) __builtin_amdgcn_s_waitcnt(wait_vm(NST2));
+  else __builtin_amdgcn_s_waitcnt(wait_vm(NST1));
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
 #pragma unroll
   for (int k = 0; k < NBW; ++k) dma_w(1, 2, k);              // item 2: k-tile 1 -> stage 2
   conv_shared(0, 0);
   asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_waitcnt(gf_wait(63));                   // (LDS writes only: the k-tile in flight stays in flight)
+  __builtin_amdgcn_s_waitcnt(wait_vm(63));                   // (LDS writes only: the k-tile in flight stays in flight)
   __builtin_amdgcn_s_barrier();                              // half 0 of the patch is published; stage 0 is free
   asm volatile("" ::: "memory");
   if (p.tlog && tid == 0 && first) p.tlog[(size_t)bid * 8 + 1] = wall_clock64();
@@ -519,7 +482,7 @@ __device__ __forceinline__ void gf_pass(const GfParams& p, const int pass, unsig
     wb = wb == 2 ? 0 : wb + 1;
     if constexpr (NEXT) {
       asm volatile("" ::: "memory");
-      __builtin_amdgcn_s_waitcnt(gf_wait(WAITN));
+      __builtin_amdgcn_s_waitcnt(wait_vm(WAITN));
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
       point();
@@ -567,8 +530,8 @@ __device__ __forceinline__ void gf_pass(const GfParams& p, const int pass, unsig
   if (save_actv) store_actv(0);
   // every wave is done with half 0 of the patch; the conv_shared weights of half 1 (requested one item ago) have landed
   asm volatile("" ::: "memory");
-  if (save_actv) __builtin_amdgcn_s_waitcnt(gf_wait(NBW + NSA));
-  else __builtin_amdgcn_s_waitcnt(gf_wait(NBW));
+  if (save_actv) __builtin_amdgcn_s_waitcnt(wait_vm(NBW + NSA));
+  else __builtin_amdgcn_s_waitcnt(wait_vm(NBW));
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
   {
@@ -581,8 +544,8 @@ __device__ __forceinline__ void gf_pass(const GfParams& p, const int pass, unsig
   }
   // publish: half 1 of the patch (LDS writes of every wave) and k-tile 18 (requested two items ago)
   asm volatile("" ::: "memory");
-  if (save_actv) __builtin_amdgcn_s_waitcnt(gf_wait(NBW + NSA));
-  else __builtin_amdgcn_s_waitcnt(gf_wait(NBW));
+  if (save_actv) __builtin_amdgcn_s_waitcnt(wait_vm(NBW + NSA));
+  else __builtin_amdgcn_s_waitcnt(wait_vm(NBW));
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
   // half 1: k-tiles 18..35; under k-tile kt request k-tile kt + 2 (<= 35)
@@ -601,7 +564,7 @@ __device__ __forceinline__ void gf_pass(const GfParams& p, const int pass, unsig
 
   // ---- epilogue.  D layout (swapped operands): lane -> pixel l31; regs 4g..4g+3 -> channels 8g + 4 lh + (0..3) of the tile
   asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_waitcnt(gf_wait(63));
+  __builtin_amdgcn_s_waitcnt(wait_vm(63));
   __builtin_amdgcn_s_barrier();                // every wave is done with the patch and the weight ring
   asm volatile("" ::: "memory");
   // the next (tile, pass) of this block: its head flies while this epilogue computes and stores
@@ -657,12 +620,12 @@ __device__ __forceinline__ void gf_pass(const GfParams& p, const int pass, unsig
         for (int k = 0; k < 2; ++k) {
           const int r = (lane_e >> 2) + 16 * k, kk = lane_e & 3;
           const f32x4 v = *reinterpret_cast<const f32x4*>(sb + r * RS + kk * 16);
-          gf_store16(v, rs, pp4[i][k] < 0 ? 0xFFFFFFF0u : (unsigned)(pp4[i][k] * dcs + dco + kk * 8) * 2u);
+          store16(v, rs, pp4[i][k] < 0 ? 0xFFFFFFF0u : (unsigned)(pp4[i][k] * dcs + dco + kk * 8) * 2u);
         }
       } else {
         const int r = lane_e >> 1, kk = lane_e & 1;
         const f32x4 v = *reinterpret_cast<const f32x4*>(sb + r * RS + kk * 16);
-        gf_store16(v, rs, pp2[i] < 0 ? 0xFFFFFFF0u : (unsigned)(pp2[i] * dcs + dco + kk * 8) * 2u);
+        store16(v, rs, pp2[i] < 0 ? 0xFFFFFFF0u : (unsigned)(pp2[i] * dcs + dco + kk * 8) * 2u);
       }
     }
   };
@@ -745,16 +708,16 @@ __device__ __forceinline__ void gf_pass(const GfParams& p, const int pass, unsig
   f32x4 xa[2][4];
   if constexpr (NPAIR >= 1) {
     load_x(0, G4{}, xa);
-    group(0, G4{}, [&](int i, int g) { return gf_acc4(acc[i][0], g); }, [&](int i, int g) { return gf_acc4(acc[i][1], g); }, xa);
+    group(0, G4{}, [&](int i, int g) { return acc4(acc[i][0], g); }, [&](int i, int g) { return acc4(acc[i][1], g); }, xa);
   }
   if constexpr (NPAIR >= 2) {
     load_x(32, G4{}, xa);
-    group(32, G4{}, [&](int i, int g) { return gf_acc4(acc[i][2], g); }, [&](int i, int g) { return gf_acc4(acc[i][3], g); }, xa);
+    group(32, G4{}, [&](int i, int g) { return acc4(acc[i][2], g); }, [&](int i, int g) { return acc4(acc[i][3], g); }, xa);
   }
   if constexpr (TAIL != 0) {
     load_x(NPAIR * 32, G2{}, xa);
-    group(NPAIR * 32, G2{}, [&](int i, int g) { return gf_acc4(acc[i][NTP - 1], g); },
-          [&](int i, int g) { return gf_acc4(acc[i][NTP - 1], g + 2); }, xa);
+    group(NPAIR * 32, G2{}, [&](int i, int g) { return acc4(acc[i][NTP - 1], g); },
+          [&](int i, int g) { return acc4(acc[i][NTP - 1], g + 2); }, xa);
   }
   if (p.tlog && tid == 0 && last) p.tlog[(size_t)bid * 8 + 6] = wall_clock64();      // every store of the tile is issued
 }
@@ -767,42 +730,20 @@ __global__ __launch_bounds__(256, 2) void spade_fused_kernel(const GfParams p, c
   if (threadIdx.x < 128)
     reinterpret_cast<float*>(smem + GF_CB_OFF)[5 * GF_CV + threadIdx.x] =
         reinterpret_cast<const float*>(reinterpret_cast<const char*>(p.wp) + GF_WSH_B)[threadIdx.x];
-  // A unit of work = one tile with the launch's passes pass0 .. pass1 one after the other (label patch loaded once) -- or, p.pp (fewer
-  // tiles than resident blocks: the 128 x 96 / 64 x 48 levels), ONE (tile, pass): the passes of a tile run on different CUs at once
-  const int npg = pass1 - pass0;
-  const int units = p.pp ? p.m_tiles * npg : p.m_tiles;
-  auto unit_tile = [&](const int u) { return p.pp ? u / npg : u; };
-  auto unit_pass = [&](const int u) { return p.pp ? pass0 + u % npg : pass0; };
-  if ((int)blockIdx.x < units) gf_head<NTP>(p, unit_pass(blockIdx.x), smem, gf_tile(p, unit_tile(blockIdx.x)), true, wave, lane);
-  int c_n = -1, c_pass = -1;                   // (image, pass) of the constants in LDS
-#pragma unroll 1
-  for (int u = blockIdx.x; u < units; u += gridDim.x) {
-    const int bid = unit_tile(u);
-    if (p.tlog && threadIdx.x == 0) {
-      unsigned hw, xcc;
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-      p.tlog[(size_t)bid * 8 + 4] = ((unsigned long long)xcc << 32) | hw;
-      p.tlog[(size_t)bid * 8 + 5] = blockIdx.x;
-    }
-    const GfTile T = gf_tile(p, bid);
-    const int nu = u + gridDim.x;
-    const GfTile TN = gf_tile(p, unit_tile(nu < units ? nu : u));
-    const int pa = unit_pass(u), pb = p.pp ? pa + 1 : pass1;
-#pragma unroll 1
-    for (int pass = pa; pass < pb; ++pass) {
-      const bool lastp = pass == pb - 1;
-      const int nxt_pass = !lastp ? pass + 1 : (nu < units ? unit_pass(nu) : -1);
-      const bool lc = c_n != T.n || c_pass != pass;
-      c_n = T.n; c_pass = pass;
-      gf_pass<NTP>(p, pass, smem, T, bid, lc, u == (int)blockIdx.x && pass == pa, p.actv != nullptr && pass == 0, pass == pa, lastp,
-                   nxt_pass, lastp ? TN : T, lastp);
-    }
-    if (p.tlog) {
-      __builtin_amdgcn_s_waitcnt(gf_wait(0));
-      if (threadIdx.x == 0) p.tlog[(size_t)bid * 8 + 3] = wall_clock64();
-    }
+  // (a tile's passes share its label patch: loaded with the first, `nxt_seg`; p.pp: the 128 x 96 / 64 x 48 levels)
+  int c_n = -1;                                // image of the constants in LDS (the scheduler keys them on the pass)
+#define GF_TILE(BID) patch_tile(BID, p.W, p.H, p.m_tiles)
+#define GF_HEAD(PASS, T) gf_head<NTP>(p, PASS, smem, T, true, wave, lane)
+#define GF_PASS(PASS, T, BID, STALE, BLOCK_FIRST, FIRST, LAST, NXT_PASS, NT_)                                            \
+  {                                                                                                                     \
+    const bool lc = c_n != T.n || STALE;                                                                                \
+    c_n = T.n;                                                                                                          \
+    gf_pass<NTP>(p, smem, PASS, T, BID, lc, BLOCK_FIRST, p.actv != nullptr && PASS == 0, FIRST, LAST, NXT_PASS, NT_, LAST); \
   }
+  PATCH_PASS_UNITS(p, pass0, pass1, GF_TILE, GF_HEAD, GF_PASS, p.tlog)
+#undef GF_TILE
+#undef GF_HEAD
+#undef GF_PASS
 }
 
 }  // namespace hrv
@@ -810,23 +751,17 @@ __global__ __launch_bounds__(256, 2) void spade_fused_kernel(const GfParams p, c
 using namespace hrv;
 
 extern "C" int64_t hrv_spade_fused_packed_bytes(int32_t C) {
-  GfPlan pl;
+  PatchPlan pl;
   if (!gf_plan(C, pl)) return -1;
   return pl.bytes;
 }
 
 extern "C" int hrv_spade_fused_supported(int32_t C, int32_t hid, int32_t label_nc, int32_t N, int32_t H, int32_t W) {
-  GfPlan pl;
+  PatchPlan pl;
   if (hid != 128 || label_nc < 1 || label_nc > 8 || !gf_plan(C, pl)) return 0;
-  const int64_t tiles = (int64_t)N * ((H + 15) / 16) * ((W + 15) / 16);
   // two blocks per CU: fewer tiles leave half the slots empty.  HRV_SPADE_FUSED_MIN_TILES_X4: the threshold in quarter-tiles per CU
   // (default 8 = two tiles per CU; A/B at 3 -- the 128 x 96 level at 4 images -- in profiles/r05_ab_fused_threshold.txt)
-  const char* e = hrv::env("HRV_SPADE_FUSED_MIN_TILES_X4");
-  int q4 = e ? atoi(e) : 8;
-  if (q4 < 1) q4 = 8;
-  // (round 6: counted in UNITS of work -- with fewer tiles than resident blocks the passes of a tile spread over the CUs)
-  const int64_t units = tiles < 2 * (int64_t)persistent_cus() ? tiles * pl.npass : tiles;
-  return 4 * units >= q4 * (int64_t)persistent_cus() ? 1 : 0;
+  return patch_units_fill(patch_tiles(N, H, W), pl.npass, "HRV_SPADE_FUSED_MIN_TILES_X4", 8);
 }
 
 extern "C" int hrv_spade_fused_pack_dev(const float* w_shared, const float* b_shared, int32_t label_nc, const float* w_gamma,
@@ -845,7 +780,7 @@ extern "C" int hrv_spade_fused_pack_dev(const float* w_shared, const float* b_sh
 
 extern "C" int hrv_spade_fused_bf16(const hrv_spade_fused_t* d, hrv_stream_t stream) {
   HRV_REQUIRE(d != nullptr, "spade_fused: null descriptor");
-  GfPlan pl;
+  PatchPlan pl;
   HRV_REQUIRE(gf_plan(d->C, pl), "spade_fused: unsupported norm width %d", d->C);
   HRV_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && (int64_t)d->N * d->H * d->W < ((int64_t)1 << 31), "spade_fused: bad extent");
   HRV_REQUIRE(d->seg && d->w_packed && d->out && d->x && d->mean && d->rstd && d->bias_gamma && d->bias_beta, "spade_fused: null pointer");
@@ -875,9 +810,8 @@ extern "C" int hrv_spade_fused_bf16(const hrv_spade_fused_t* d, hrv_stream_t str
   p.seg = d->seg; p.seg_H = d->seg_H; p.seg_W = d->seg_W; p.seg_shift = d->seg_shift; p.seg_bytes = (unsigned)sbytes;
   p.N = d->N; p.H = d->H; p.W = d->W;
   p.wp = d->w_packed; p.w_bytes = (unsigned)pl.bytes;
-  p.npass = pl.npass;
-  for (int i = 0; i < pl.npass; ++i) { p.ntp[i] = pl.ntp[i]; p.tile0[i] = pl.tile0[i]; p.woff[i] = pl.woff[i]; }
-  p.m_tiles = d->N * ((d->H + 15) / 16) * ((d->W + 15) / 16);
+  patch_plan_copy(p, pl);
+  p.m_tiles = (int)patch_tiles(d->N, d->H, d->W);
   p.sx = (const float*)d->x; p.sx_cs = d->x_cstride; p.sx_co = d->x_coff; p.sx_f32 = d->x_f32; p.sC = d->C;
   p.sx2 = (const float*)d->x2; p.sx2_cs = d->x2_cstride; p.sx2_co = d->x2_coff; p.sx_up_c = d->x_up_channels;
   p.smean = d->mean; p.srstd = d->rstd; p.sz = d->noise_z; p.sns = d->noise_scale; p.bg = d->bias_gamma; p.bb = d->bias_beta;
@@ -886,19 +820,13 @@ extern "C" int hrv_spade_fused_bf16(const hrv_spade_fused_t* d, hrv_stream_t str
   p.out = d->out; p.out_cs = d->out_cstride; p.out_co = d->out_coff;
   p.actv = d->actv; p.actv_cs = d->actv_cstride; p.actv_co = d->actv_coff;
   p.tlog = diag_tlog(p.m_tiles);
-  const int cap = 2 * persistent_cus();
-  p.pp = p.m_tiles < cap ? 1 : 0;
+  p.pp = patch_pp(p.m_tiles) ? 1 : 0;
   if (p.pp) p.tlog = nullptr;          // (the timeline's slots are per tile)
-  // the passes of equal width share a launch: 4-tile passes, a 2-tile pass, the 5-tile tail pass
-  for (int a = 0; a < pl.npass;) {
-    int b = a;
-    while (b < pl.npass && pl.ntp[b] == pl.ntp[a]) ++b;
-    const long long units = p.pp ? (long long)p.m_tiles * (b - a) : p.m_tiles;
-    const int grid = units < cap ? (int)units : cap;
+  // 4-tile passes, a 2-tile pass, the 5-tile tail pass
+  patch_pass_groups(pl, p.m_tiles, p.pp != 0, [](int) { return 2; }, [&](const int a, const int b, const int grid) {
     if (pl.ntp[a] == 4) hipLaunchKernelGGL((spade_fused_kernel<4>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p, a, b);
     else if (pl.ntp[a] == 2) hipLaunchKernelGGL((spade_fused_kernel<2>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p, a, b);
     else hipLaunchKernelGGL((spade_fused_kernel<5>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p, a, b);
-    a = b;
-  }
+  });
   return check_launch("spade_fused_kernel");
 }

@@ -31,33 +31,16 @@
 #include <type_traits>
 #include <utility>
 
-#include "conv_params.h"
+#include "patch_pass.h"
 
 namespace hrv {
 
 // compile-time loop (the scheduling hints take literal arguments)
-#if defined(__HIP_DEVICE_COMPILE__)
-__device__ __forceinline__ void gb_store16(f32x4 v, rsrc_t r, unsigned voff) {
-  typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), r, (int)voff, 0, 0);
-}
-#else
-__device__ inline void gb_store16(f32x4, rsrc_t, unsigned) {}
-#endif
-
-// registers 4g .. 4g+3 of an accumulator tile (4 consecutive output channels of the lane's pixel)
-__device__ __forceinline__ f32x4 gb_acc4(const f32x16& a, int g) {
-  f32x4 r;
-  r[0] = a[4 * g]; r[1] = a[4 * g + 1]; r[2] = a[4 * g + 2]; r[3] = a[4 * g + 3];
-  return r;
-}
-
 template <typename F, int... Is>
 __device__ __forceinline__ void gb_static_for(std::integer_sequence<int, Is...>, F&& f) {
   (f(std::integral_constant<int, Is>{}), ...);
 }
 
-constexpr int GB_MAXP = 16;
 constexpr int GB_PW = 20;                      // patch row pitch in pixels (18 + 2: a row is five 4-pixel DMA pieces)
 constexpr int GB_PATCH_B = 18 * GB_PW * 256;
 constexpr int GB_SBMAX = 5 * 4096;
@@ -70,9 +53,9 @@ struct GbParams {
   int N, H, W, M;
   const void* wp; unsigned w_bytes;
   int npass;
-  int ntp[GB_MAXP];         // column tiles of 32 per pass (4 or 5)
-  int tile0[GB_MAXP];       // first column tile of the pass
-  unsigned woff[GB_MAXP];   // byte offset of the pass's weight block
+  int ntp[PATCH_MAXP];         // column tiles of 32 per pass (4 or 5)
+  int tile0[PATCH_MAXP];       // first column tile of the pass
+  unsigned woff[PATCH_MAXP];   // byte offset of the pass's weight block
   int nchunk, KT;           // 128-channel chunks of the source; K-tiles (chunk, tap, 64-k half) per pass
   int m_tiles;
   // forward (SPADE modulate) epilogue
@@ -84,12 +67,12 @@ struct GbParams {
   // data-gradient epilogue
   const void* mask; int mask_cs, mask_co;
   unsigned long long* tlog;
-  int stagger_ticks;        // 100 MHz ticks between the phase groups' starts (0: none)
 };
 
+// (PatchPlan with KT, in the member order gb_pack_kernel has always read by value)
 struct GbPlan {
-  int npass, ntp[GB_MAXP], tile0[GB_MAXP], nchunk, KT;
-  unsigned woff[GB_MAXP];
+  int npass, ntp[PATCH_MAXP], tile0[PATCH_MAXP], nchunk, KT;
+  unsigned woff[PATCH_MAXP];
   long long bytes;
 };
 
@@ -113,7 +96,7 @@ static bool gb_plan(int mode, int C, int Cp, int hid, GbPlan& pl) {
   if (rest < 0) return false;
   const int n2 = (rest % 4 == 2) ? 1 : 0;
   const int n4 = (rest - 2 * n2) / 4;
-  if (n4 + n2 + n5 > GB_MAXP || n4 + n2 + n5 < 1) return false;
+  if (n4 + n2 + n5 > PATCH_MAXP || n4 + n2 + n5 < 1) return false;
   pl.npass = n4 + n2 + n5;
   pl.nchunk = (Cs + 127) / 128;
   {
@@ -205,9 +188,6 @@ __global__ __launch_bounds__(256) void gb_pack_kernel(const GbPackParams p) {
 }
 
 // ------------------------------------------------------------------------------------------------ the kernel
-// s_waitcnt immediates (gfx9 encoding: vmcnt[3:0] bits 3:0, expcnt bits 6:4, lgkmcnt bits 11:8, vmcnt[5:4] bits 15:14)
-constexpr int gb_wait(int vm) { return (vm & 15) | (7 << 4) | (0 << 8) | ((vm >> 4) << 14); }   // vmcnt(vm) lgkmcnt(0)
-
 // Everything one (tile, pass) needs before its main loop: the halo patch (chunk 0) and weight tiles 0, 1 of the pass.
 // Issued by the PREVIOUS pass's epilogue (after the barrier that frees the patch and ring stages 0 / 1), so the loads fly
 // while that epilogue computes and stores.
@@ -263,24 +243,12 @@ struct GbIssue {
   }
 };
 
-struct GbTile { int n, y0, x0; };
-__device__ __forceinline__ GbTile gb_tile(const GbParams& p, int bid) {
-  const int tx = (p.W + 15) >> 4, ty = (p.H + 15) >> 4;
-  const int mt = xcd_remap(bid, p.m_tiles);
-  GbTile t;
-  t.n = mt / (tx * ty);
-  const int rr = mt - t.n * (tx * ty);
-  t.y0 = (rr / tx) << 4;
-  t.x0 = (rr % tx) << 4;
-  return t;
-}
-
 // One (tile, pass).  On entry its patch / weight tiles 0, 1 are in flight or landed (GbIssue::issue); ``nxt_*`` describe
 // what to issue for the next (tile, pass) of this block once the main loop is done (nxt_pass < 0: nothing).
 template <int NTP, int EPI, bool HALF>
-__device__ __forceinline__ void gb_pass(const GbParams& p, const int pass, unsigned char* const smem, const GbTile T,
+__device__ __forceinline__ void gb_pass(const GbParams& p, const int pass, unsigned char* const smem, const PatchTile T,
                                         const int bid, const bool first, const bool last, const int nxt_pass, const bool nxt_patch,
-                                        const GbTile NT_) {
+                                        const PatchTile NT_) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, lh = lane >> 5;
@@ -339,7 +307,7 @@ __device__ __forceinline__ void gb_pass(const GbParams& p, const int pass, unsig
     }
   }
   // the patch and weight tiles 0, 1 (issued before this call) have landed
-  __builtin_amdgcn_s_waitcnt(gb_wait(0));
+  __builtin_amdgcn_s_waitcnt(wait_vm(0));
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
   if (p.tlog && tid == 0 && first) p.tlog[(size_t)bid * 8 + 1] = wall_clock64();
@@ -470,8 +438,8 @@ __device__ __forceinline__ void gb_pass(const GbParams& p, const int pass, unsig
       rb = rb == 2 ? 0 : rb + 1;
       wb = wb == 2 ? 0 : wb + 1;
       asm volatile("" ::: "memory");
-      if (more) __builtin_amdgcn_s_waitcnt(gb_wait(NB));
-      else __builtin_amdgcn_s_waitcnt(gb_wait(0));
+      if (more) __builtin_amdgcn_s_waitcnt(wait_vm(NB));
+      else __builtin_amdgcn_s_waitcnt(wait_vm(0));
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
       if constexpr (EPI == 2) {
@@ -489,7 +457,7 @@ __device__ __forceinline__ void gb_pass(const GbParams& p, const int pass, unsig
         GB_MMA((NKS - 1) & 1)
         if (new_chunk) {
           asm volatile("" ::: "memory");
-          __builtin_amdgcn_s_waitcnt(gb_wait(0));
+          __builtin_amdgcn_s_waitcnt(wait_vm(0));
           __builtin_amdgcn_s_barrier();
           asm volatile("" ::: "memory");
           point();
@@ -564,7 +532,7 @@ __device__ __forceinline__ void gb_pass(const GbParams& p, const int pass, unsig
         const f32x4 lo = *reinterpret_cast<const f32x4*>(scr + r * SCS + kk * 8);
         const f32x4 hi = *reinterpret_cast<const f32x4*>(scr + r * SCS + kk * 8 + 4);
         const unsigned ro = row_off(i, r, dcs, 2);
-        gb_store16(pack_bf16x8(lo, hi), rs, ro == 0xFFFFFFF0u ? ro : ro + (unsigned)(dco + kk * 8) * 2u);
+        store16(pack_bf16x8(lo, hi), rs, ro == 0xFFFFFFF0u ? ro : ro + (unsigned)(dco + kk * 8) * 2u);
       }
     } else {
 #pragma unroll
@@ -572,7 +540,7 @@ __device__ __forceinline__ void gb_pass(const GbParams& p, const int pass, unsig
         const int t = lane_e + 64 * k, r = t >> (SH + 1), kk = t & (2 * NG - 1);
         const f32x4 v = *reinterpret_cast<const f32x4*>(scr + r * SCS + kk * 4);
         const unsigned ro = row_off(i, r, dcs, 4);
-        gb_store16(v, rs, ro == 0xFFFFFFF0u ? ro : ro + (unsigned)(dco + kk * 4) * 4u);
+        store16(v, rs, ro == 0xFFFFFFF0u ? ro : ro + (unsigned)(dco + kk * 4) * 4u);
       }
     }
   };
@@ -607,12 +575,12 @@ __device__ __forceinline__ void gb_pass(const GbParams& p, const int pass, unsig
         for (int k = 0; k < 2; ++k) {
           const int r = (lane_e >> 2) + 16 * k, kk = lane_e & 3;
           const f32x4 v = *reinterpret_cast<const f32x4*>(sb + r * RS + kk * 16);
-          gb_store16(v, rs, pp4[i][k] < 0 ? 0xFFFFFFF0u : (unsigned)(pp4[i][k] * dcs + dco + kk * 8) * 2u);
+          store16(v, rs, pp4[i][k] < 0 ? 0xFFFFFFF0u : (unsigned)(pp4[i][k] * dcs + dco + kk * 8) * 2u);
         }
       } else {
         const int r = lane_e >> 1, kk = lane_e & 1;
         const f32x4 v = *reinterpret_cast<const f32x4*>(sb + r * RS + kk * 16);
-        gb_store16(v, rs, pp2[i] < 0 ? 0xFFFFFFF0u : (unsigned)(pp2[i] * dcs + dco + kk * 8) * 2u);
+        store16(v, rs, pp2[i] < 0 ? 0xFFFFFFF0u : (unsigned)(pp2[i] * dcs + dco + kk * 8) * 2u);
       }
     }
   };
@@ -666,11 +634,11 @@ __device__ __forceinline__ void gb_pass(const GbParams& p, const int pass, unsig
     using G2 = std::integral_constant<int, 2>;
 #pragma unroll
     for (int pr = 0; pr < NPAIR; ++pr)
-      group(pr * 32, G4{}, [&](int i, int g) { return gb_acc4(acc[i][2 * pr], g); },
-            [&](int i, int g) { return gb_acc4(acc[i][2 * pr + 1], g); }, [&](int i, int g) { return xv[i][pr][g]; });
+      group(pr * 32, G4{}, [&](int i, int g) { return acc4(acc[i][2 * pr], g); },
+            [&](int i, int g) { return acc4(acc[i][2 * pr + 1], g); }, [&](int i, int g) { return xv[i][pr][g]; });
     if constexpr (TAIL != 0)
-      group(NPAIR * 32, G2{}, [&](int i, int g) { return gb_acc4(acc[i][NTP - 1], g); },
-            [&](int i, int g) { return gb_acc4(acc[i][NTP - 1], g + 2); }, [&](int i, int g) { return xt[i][g]; });
+      group(NPAIR * 32, G2{}, [&](int i, int g) { return acc4(acc[i][NTP - 1], g); },
+            [&](int i, int g) { return acc4(acc[i][NTP - 1], g + 2); }, [&](int i, int g) { return xt[i][g]; });
   } else {
     using G4 = std::integral_constant<int, 4>;
     if (!p.out_f32) {
@@ -681,7 +649,7 @@ __device__ __forceinline__ void gb_pass(const GbParams& p, const int pass, unsig
         for (int g = 0; g < 4; ++g)
 #pragma unroll
           for (int i = 0; i < 2; ++i) {
-            f32x4 v = gb_acc4(acc[i][j], g);
+            f32x4 v = acc4(acc[i][j], g);
             if (p.mask) {
 #pragma unroll
               for (int e = 0; e < 4; ++e) v[e] = bf2f(mv[i][j][g][e]) > 0.f ? v[e] : v[e] * p.slope;
@@ -721,41 +689,23 @@ __global__ __launch_bounds__(256) void spade_gb_kernel(const GbParams p, const i
   __shared__ __attribute__((aligned(1024))) unsigned char smem[GB_LDS];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
   const bool repatch = p.nchunk > 1;           // a multi-chunk source's patch holds its LAST chunk when a pass ends
-  // Staggered start.  Every tile is a compute phase (main loop, HBM idle) followed by a memory phase (epilogue stores,
-  // the next tile's patch and x: ~280 KB per tile); blocks that start together stay in lock step, so all 256 CUs hit HBM
-  // at once and then leave it idle (measured: a 14 us memory phase = 256 x 283 KB at HBM speed, next to a 19 us main
-  // loop).  Four phase groups, a quarter of a tile apart, spread the memory phases over the compute phases.
-  if (p.stagger_ticks > 0) {
-    const unsigned long long t_go = wall_clock64() + (unsigned long long)((blockIdx.x >> 3) & 3) * (unsigned)p.stagger_ticks;
-    while (wall_clock64() < t_go) __builtin_amdgcn_s_sleep(32);
-  }
   if ((int)blockIdx.x < p.m_tiles) {
-    const GbTile T0 = gb_tile(p, blockIdx.x);
+    const PatchTile T0 = patch_tile(blockIdx.x, p.W, p.H, p.m_tiles);
     GbIssue<NTP>::issue(p, smem, pass0, true, T0.n, T0.y0, T0.x0, wave, lane);
   }
 #pragma unroll 1
   for (int bid = blockIdx.x; bid < p.m_tiles; bid += gridDim.x) {
-    if (p.tlog && threadIdx.x == 0) {
-      unsigned hw, xcc;
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-      p.tlog[(size_t)bid * 8 + 0] = wall_clock64();
-      p.tlog[(size_t)bid * 8 + 4] = ((unsigned long long)xcc << 32) | hw;
-      p.tlog[(size_t)bid * 8 + 5] = blockIdx.x;
-    }
-    const GbTile T = gb_tile(p, bid);
+    if (p.tlog && threadIdx.x == 0) tlog_where(p.tlog, bid, true);
+    const PatchTile T = patch_tile(bid, p.W, p.H, p.m_tiles);
     const int nbid = bid + gridDim.x;
-    const GbTile TN = gb_tile(p, nbid < p.m_tiles ? nbid : bid);
+    const PatchTile TN = patch_tile(nbid < p.m_tiles ? nbid : bid, p.W, p.H, p.m_tiles);
 #pragma unroll 1
     for (int pass = pass0; pass < pass1; ++pass) {
       const bool lastp = pass == pass1 - 1;
       const int nxt_pass = !lastp ? pass + 1 : (nbid < p.m_tiles ? pass0 : -1);
       gb_pass<NTP, EPI, HALF>(p, pass, smem, T, bid, pass == pass0, lastp, nxt_pass, lastp || repatch, lastp ? TN : T);
     }
-    if (p.tlog) {
-      __builtin_amdgcn_s_waitcnt(gb_wait(0));
-      if (threadIdx.x == 0) p.tlog[(size_t)bid * 8 + 3] = wall_clock64();
-    }
+    TLOG_DRAINED(p.tlog, bid)
   }
 }
 
@@ -772,7 +722,7 @@ extern "C" int64_t hrv_spade_gb_packed_bytes(int32_t mode, int32_t C, int32_t Cp
 extern "C" int hrv_spade_gb_supported(int32_t mode, int32_t C, int32_t Cp, int32_t hid, int32_t N, int32_t H, int32_t W) {
   GbPlan pl;
   if (!gb_plan(mode, C, Cp, hid, pl)) return 0;
-  const int64_t tiles = (int64_t)N * ((H + 15) / 16) * ((W + 15) / 16);
+  const int64_t tiles = patch_tiles(N, H, W);
   // fewer tiles than CUs: the generic tiles (more, smaller blocks; split-K) fill the chip better.  HRV_SPADE_GB_MIN_TILES: the threshold
   const char* e = hrv::env("HRV_SPADE_GB_MIN_TILES");
   int tmin = e ? atoi(e) : 256;
@@ -811,9 +761,9 @@ extern "C" int hrv_spade_gb_bf16(const hrv_spade_gb_t* d, hrv_stream_t stream) {
   p.src = d->src; p.src_cs = d->src_cstride; p.src_co = d->src_coff; p.C = Cs; p.src_bytes = (unsigned)sbytes;
   p.N = d->N; p.H = d->H; p.W = d->W; p.M = d->N * d->H * d->W;
   p.wp = d->w_packed; p.w_bytes = (unsigned)pl.bytes;
-  p.npass = pl.npass; p.nchunk = pl.nchunk; p.KT = pl.KT;
-  for (int i = 0; i < pl.npass; ++i) { p.ntp[i] = pl.ntp[i]; p.tile0[i] = pl.tile0[i]; p.woff[i] = pl.woff[i]; }
-  p.m_tiles = d->N * ((d->H + 15) / 16) * ((d->W + 15) / 16);
+  patch_plan_copy(p, pl);
+  p.nchunk = pl.nchunk; p.KT = pl.KT;
+  p.m_tiles = (int)patch_tiles(d->N, d->H, d->W);
   p.out = d->out; p.out_cs = d->out_cstride; p.out_co = d->out_coff; p.out_f32 = d->out_f32;
   p.act = d->act; p.slope = d->act_slope;
   const int oal = d->out_f32 ? 4 : 8;
@@ -822,9 +772,8 @@ extern "C" int hrv_spade_gb_bf16(const hrv_spade_gb_t* d, hrv_stream_t stream) {
   // over through hrv_diag_set_tlog (never read from the environment: a stray variable must not turn the hottest
   // kernel of the iteration into a scribbler on arbitrary device memory)
   p.tlog = diag_tlog(p.m_tiles);
-  int grid = persistent_cus();
-  if (grid > p.m_tiles) grid = p.m_tiles;
-  p.stagger_ticks = 0;      // (staggered block starts measured no gain: the epilogue is issue-bound, not HBM-bound)
+  // one block per CU, a unit of work is always a whole tile
+  const auto one_per_cu = [](int) { return 1; };
   if (d->mode == 0) {
     HRV_REQUIRE(d->x && d->mean && d->rstd && d->bias_gamma && d->bias_beta, "spade_gb: null epilogue pointer");
     HRV_REQUIRE((d->noise_z == nullptr) == (d->noise_scale == nullptr), "spade_gb: noise_z/noise_scale go together");
@@ -839,21 +788,20 @@ extern "C" int hrv_spade_gb_bf16(const hrv_spade_gb_t* d, hrv_stream_t stream) {
     p.smean = d->mean; p.srstd = d->rstd; p.sz = d->noise_z; p.sns = d->noise_scale; p.bg = d->bias_gamma; p.bb = d->bias_beta;
     p.g1p = d->g1p; p.g1_bf16 = d->g1p_bf16;
     // the passes of equal width share a launch (the patch stays resident across them): 4-tile passes, a 2-tile pass, the 5-tile tail pass
-    for (int a = 0; a < pl.npass;) {
-      int b = a;
-      while (b < pl.npass && pl.ntp[b] == pl.ntp[a]) ++b;
+    patch_pass_groups(pl, p.m_tiles, false, one_per_cu, [&](const int a, const int b, const int grid) {
       if (pl.ntp[a] == 4) hipLaunchKernelGGL((spade_gb_kernel<4, 1, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p, a, b);
       else if (pl.ntp[a] == 2) hipLaunchKernelGGL((spade_gb_kernel<2, 1, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p, a, b);
       else hipLaunchKernelGGL((spade_gb_kernel<5, 1, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p, a, b);
-      a = b;
-    }
+    });
   } else {
     HRV_REQUIRE(d->out_cstride >= d->out_coff + d->hid, "spade_gb: out slice");
     HRV_REQUIRE(d->mask == nullptr || (d->mask_cstride % 4 == 0 && d->mask_coff % 4 == 0 && ((uintptr_t)d->mask & 7) == 0),
                 "spade_gb: mask slice");
     p.mask = d->mask; p.mask_cs = d->mask_cstride; p.mask_co = d->mask_coff;
-    if ((p.C & 127) == 32) hipLaunchKernelGGL((spade_gb_kernel<4, 2, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p, 0, 1);
-    else hipLaunchKernelGGL((spade_gb_kernel<4, 2, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p, 0, 1);
+    patch_pass_groups(pl, p.m_tiles, false, one_per_cu, [&](const int a, const int b, const int grid) {      // (one pass of 4)
+      if ((p.C & 127) == 32) hipLaunchKernelGGL((spade_gb_kernel<4, 2, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p, a, b);
+      else hipLaunchKernelGGL((spade_gb_kernel<4, 2, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p, a, b);
+    });
   }
   return check_launch("spade_gb_kernel");
 }

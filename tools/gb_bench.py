@@ -64,14 +64,10 @@ def main():
         fl = 2.0 * N * H * W * 2 * Cc * 128 * 9
         print(f"{name}: C={Cc} N={N} {H}x{W}  ({fl / 1e12:.3f} TFLOP per launch)")
         for what, fn in (("forward", fwd), ("dgrad", dgrad)):
-            times = {"1": [], "0": [], "ns": []}
+            times = {"1": [], "0": []}
             for rd in range(rounds + 2):
-                for flag in ("1", "0", "ns"):
-                    os.environ["HRV_SPADE_GB"] = "0" if flag == "0" else "1"
-                    if flag == "ns":
-                        os.environ["HRV_GB_STAGGER"] = "0"
-                    else:
-                        os.environ.pop("HRV_GB_STAGGER", None)
+                for flag in ("1", "0"):
+                    os.environ["HRV_SPADE_GB"] = flag
                     s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     s.record()
                     fn()
@@ -79,8 +75,7 @@ def main():
                     torch.cuda.synchronize()
                     if rd >= 2:
                         times[flag].append(s.elapsed_time(e))
-            os.environ.pop("HRV_GB_STAGGER", None)
-            for flag, lab in (("1", "spade_gb kernel"), ("ns", "spade_gb, no stagger"), ("0", "generic patch tiles")):
+            for flag, lab in (("1", "spade_gb kernel"), ("0", "generic patch tiles")):
                 ts = sorted(times[flag])
                 med = ts[len(ts) // 2]
                 print(f"   {what:8s} {lab:20s} median {med:7.3f} ms  min {ts[0]:7.3f}  {fl / (med * 1e-3) / 1e12:7.1f} TFLOP/s "
