@@ -17,6 +17,12 @@ batches.  Differences from the reference script:
     printed when the two counts differ.
   * MSE is written as a plain float (the reference's f-string prints the CUDA tensor).
   * non-image files in --predict_dir (e.g. the lpips.txt / eval.txt of an earlier run) are skipped.
+  * ``--fid`` adds what the paper reports for the unpaired setting and the reference script does not compute: FID and KID between
+    ALL images of --predict_dir and ALL images of --ground_truth_dir (no pairing), on pytorch-fid's Inception-v3
+    (``--fid_inception_weights``, default torch's hub-cache ``pt_inception-2015-12-05-6726825d.pth``, never downloaded; without the
+    file the values are written as nan, ``--fid_random_init`` runs on seeded random weights and says so) with torch-fidelity's KID
+    subsets (``--kid_subsets`` x ``--kid_subset_size``).  One more line goes to eval.txt.  ``--fid_only`` computes nothing else: no
+    pairing, no LPIPS weights, lpips.txt untouched.  The workers only decode for this metric; the 299x299 resize is the input kernel's.
 The reference's quirk of dividing the three averages by the number of ground-truth files is kept, so the numbers stay
 comparable; a note is printed when that count differs from the number of predictions.
 """
@@ -36,6 +42,7 @@ if ROOT not in sys.path:
 IMAGE_EXT = (".jpg", ".jpeg", ".png", ".bmp", ".webp", ".tif", ".tiff")
 ALEXNET_FILE = "alexnet-owt-7be5be79.pth"
 INCEPTION_FILES = ("inception_v3_google-0cc3c7bd.pth", "inception_v3_google-1a9a5a14.pth")    # torchvision's, newer release first
+FID_INCEPTION_FILE = "pt_inception-2015-12-05-6726825d.pth"                                   # pytorch-fid's / torch-fidelity's
 
 
 def _default_alexnet_weights():
@@ -48,7 +55,7 @@ def _default_inception_weights():
     return next((p for p in paths if os.path.isfile(p)), paths[0])
 
 
-def get_opt(argv=None):
+def _parser():
     p = argparse.ArgumentParser()
     p.add_argument("--evaluation", default="LPIPS", help="parsed and unused, as in the reference")
     p.add_argument("--predict_dir", default="./result/bg_ver1/output/")
@@ -69,6 +76,21 @@ def get_opt(argv=None):
                    help="torch seed of the random initialisations (--lpips_random_init, --inception_random_init)")
     p.add_argument("-j", "--workers", type=int, default=4)
     p.add_argument("-b", "--batch-size", type=int, default=16)
+    p.add_argument("--fid", action="store_true",
+                   help="also score FID and KID between all images of --predict_dir and all of --ground_truth_dir (no pairing)")
+    p.add_argument("--fid_only", action="store_true", help="FID and KID alone: no pairing, no SSIM / MSE / LPIPS / IS")
+    p.add_argument("--fid_inception_weights", default=None,
+                   help="the FID Inception-v3 state dict (default: torch's hub cache, %s; without the file the values are written "
+                        "as nan)" % FID_INCEPTION_FILE)
+    p.add_argument("--fid_random_init", action="store_true",
+                   help="plumbing only: FID / KID on a randomly initialised network (the output is labelled)")
+    p.add_argument("--kid_subsets", type=int, default=100, help="KID subsets (torch-fidelity's default)")
+    p.add_argument("--kid_subset_size", type=int, default=1000, help="images per KID subset (torch-fidelity's default)")
+    return p
+
+
+def get_opt(argv=None):
+    p = _parser()
     opt = p.parse_args(argv)
     if opt.alexnet_weights is None:
         opt.alexnet_weights = _default_alexnet_weights()
@@ -76,6 +98,10 @@ def get_opt(argv=None):
         opt.inception_weights = _default_inception_weights()
     if opt.is_splits < 1:
         p.error("--is_splits must be at least 1")
+    if opt.fid_inception_weights is None:
+        opt.fid_inception_weights = os.path.join(torch.hub.get_dir(), "checkpoints", FID_INCEPTION_FILE)
+    if opt.kid_subsets < 1 or opt.kid_subset_size < 2:
+        p.error("--kid_subsets must be at least 1 and --kid_subset_size at least 2")
     return opt
 
 
@@ -225,6 +251,124 @@ class GpuScorer:
         return list(zip(ssim, mse, [float(v) for v in lp.cpu().tolist()]))
 
 
+# ------------------------------------------------------------------------------------------------------------------ FID / KID
+class ImageDataset(torch.utils.data.Dataset):
+    """Images of one folder as decoded, RGB uint8; ``resolution``: the ground truths' resize of the paired path (512, 256) or None."""
+
+    def __init__(self, folder, names, resolution=None):
+        self.folder, self.names, self.resolution = folder, names, resolution
+
+    def __len__(self):
+        return len(self.names)
+
+    def __getitem__(self, i):
+        img = Image.open(os.path.join(self.folder, self.names[i]))
+        if self.resolution == 512:
+            img = img.resize((384, 512), Image.BILINEAR)
+        elif self.resolution == 256:
+            img = img.resize((192, 256), Image.BILINEAR)
+        return {"name": self.names[i], "img": _rgb(img)}
+
+
+def load_fid_inception(opt):
+    """(FIDInceptionV3 or None, random_init), as load_inception: the file, else seeded random weights when asked, else None."""
+    have = os.path.isfile(opt.fid_inception_weights)
+    if not have and not opt.fid_random_init:
+        return None, False
+    import hr_viton_amd  # noqa: F401
+    from hr_viton_amd.inception import FIDInceptionV3
+    torch.manual_seed(opt.seed)
+    model = FIDInceptionV3()
+    if have:
+        model.load_state_dict(torch.load(opt.fid_inception_weights, map_location="cpu"))
+    else:
+        print("WARNING: FID / KID run on a RANDOMLY initialised Inception-v3 (--fid_random_init): they are not the paper's metrics",
+              file=sys.stderr, flush=True)
+    model.eval()
+    return model, not have
+
+
+class FidScorer:
+    """The GPU side of --fid: two feature banks that stay on the device, rows filled batch by batch, and their statistics."""
+
+    WIDTH = 2048
+
+    def __init__(self, model):
+        from hr_viton_amd import feat_stats
+        self.model, self.stats = model, feat_stats
+        self.dev = torch.device("cuda")
+
+    def bank(self, n):
+        return torch.empty((n, self.WIDTH), dtype=torch.float32, device=self.dev)
+
+    def fill(self, bank, row0, batch):
+        """features of a loader batch into bank[row0 : row0 + len(batch)]; images of one size go through the network together"""
+        groups = {}
+        for i, it in enumerate(batch):
+            groups.setdefault(it["img"].shape, []).append(i)
+        for idx in groups.values():
+            x = torch.from_numpy(np.stack([batch[i]["img"] for i in idx])).pin_memory().to(self.dev, non_blocking=True)
+            if len(groups) == 1:
+                self.model.features_u8(x, out=bank[row0:row0 + len(batch)])
+            else:
+                bank[torch.as_tensor(idx, device=self.dev) + row0] = self.model.features_u8(x)
+
+    def score(self, bank_pred, bank_gt, subsets, subset_size):
+        return self.stats.fid_kid(bank_pred, bank_gt, subsets, subset_size)
+
+
+def fid_evaluation(opt, pred_list, gt_images, fid_scorer):
+    """(fid, kid_mean, kid_std, timings) between all predictions and all ground truths."""
+    t0 = time.perf_counter()
+    banks = []
+    print("Calculate FID, KID...")
+    for folder, names, res in ((opt.predict_dir, pred_list, None),
+                               (opt.ground_truth_dir, gt_images, opt.resolution if opt.resolution != 1024 else None)):
+        loader = torch.utils.data.DataLoader(ImageDataset(folder, names, res), batch_size=max(1, opt.batch_size), shuffle=False,
+                                             num_workers=opt.workers, collate_fn=list)
+        bank, row = fid_scorer.bank(len(names)), 0
+        for batch in loader:
+            fid_scorer.fill(bank, row, batch)
+            row += len(batch)
+        banks.append(bank)
+    t1 = time.perf_counter()
+    fid, kid_mean, kid_std = fid_scorer.score(banks[0], banks[1], opt.kid_subsets, opt.kid_subset_size)
+    return float(fid), float(kid_mean), float(kid_std), {"fid_features_s": t1 - t0, "fid_stats_s": time.perf_counter() - t1}
+
+
+def write_fid(predict_dir, fid, kid_mean, kid_std, random_init=False):
+    with open(os.path.join(predict_dir, "eval.txt"), "a") as f:
+        f.write(f"FID : {fid} / KID_mean : {kid_mean} / KID_std : {kid_std}\n")
+        if random_init:
+            f.write("FID Inception weights : random init (plumbing only)\n")
+
+
+def run_fid(opt, pred_list, fid_scorer=None):
+    """The --fid / --fid_only part of main(): returns the dict entries and writes eval.txt's extra line."""
+    gt_images = list_predictions(opt.ground_truth_dir)
+    if opt.kid_subset_size > min(len(pred_list), len(gt_images)):
+        _parser().error(f"--kid_subset_size {opt.kid_subset_size} is larger than an image set: {len(pred_list)} predictions in "
+                        f"{opt.predict_dir}, {len(gt_images)} ground truths in {opt.ground_truth_dir}")
+    random_init = fid_scorer is not None and opt.fid_random_init
+    if fid_scorer is None:
+        model, random_init = load_fid_inception(opt)
+        if model is not None:
+            fid_scorer = FidScorer(model)
+    timings = {}
+    if fid_scorer is None:
+        print("FID / KID: not computed (they need the FID Inception-v3: --fid_inception_weights, now %r, does not exist and nothing "
+              "is downloaded; --fid_random_init for plumbing runs): written as nan" % opt.fid_inception_weights, file=sys.stderr)
+        fid = kid_mean = kid_std = float("nan")
+    else:
+        with torch.no_grad():
+            fid, kid_mean, kid_std, timings = fid_evaluation(opt, pred_list, gt_images, fid_scorer)
+    write_fid(opt.predict_dir, fid, kid_mean, kid_std, random_init)
+    print("FID : %f / KID_mean : %f / KID_std : %f" % (fid, kid_mean, kid_std))
+    if random_init:
+        print("(FID / KID from randomly initialised weights: plumbing only)")
+    return {"fid": fid, "kid_mean": kid_mean, "kid_std": kid_std, "fid_images": [len(pred_list), len(gt_images)]}, timings
+
+
 def write_results(predict_dir, lpips_list, avg_ssim, avg_mse, avg_distance, is_mean, is_std, random_init=False,
                   inception_random_init=False):
     lpips_list = sorted(lpips_list, key=lambda x: x[1], reverse=True)
@@ -284,11 +428,15 @@ def evaluation(opt, pred_list, gt_list, scorer, is_scorer=None):
     return sum_ssim / n, sum_mse / n, sum_dist / n, lpips_list, timings
 
 
-def main(argv=None, scorer=None, is_scorer=None):
-    """``scorer`` / ``is_scorer``: stand-ins for GpuScorer / InceptionScorer (tests).  With a ``scorer`` and no ``is_scorer`` nothing
-    is loaded and the Inception Score is nan."""
+def main(argv=None, scorer=None, is_scorer=None, fid_scorer=None):
+    """``scorer`` / ``is_scorer`` / ``fid_scorer``: stand-ins for GpuScorer / InceptionScorer / FidScorer (tests).  With a ``scorer``
+    and no ``is_scorer`` nothing is loaded and the Inception Score is nan."""
     opt = get_opt(argv)
     pred_list = list_predictions(opt.predict_dir)
+    if opt.fid_only:
+        res, timings = run_fid(opt, pred_list, fid_scorer)
+        res["timings"] = timings
+        return res
     gt_list = sorted(os.listdir(opt.ground_truth_dir))
     random_init = False
     is_random_init = is_scorer is not None and opt.inception_random_init
@@ -323,8 +471,13 @@ def main(argv=None, scorer=None, is_scorer=None):
         print("(LPIPS from randomly initialised weights: plumbing only)")
     if is_random_init:
         print("(Inception Score from randomly initialised weights: plumbing only)")
-    return {"ssim": avg_ssim, "mse": avg_mse, "lpips": avg_distance, "is_mean": is_mean, "is_std": is_std, "pairs": len(pred_list),
-            "timings": timings}
+    res = {"ssim": avg_ssim, "mse": avg_mse, "lpips": avg_distance, "is_mean": is_mean, "is_std": is_std, "pairs": len(pred_list),
+           "timings": timings}
+    if opt.fid:
+        fid_res, fid_timings = run_fid(opt, pred_list, fid_scorer)
+        res.update(fid_res)
+        timings.update(fid_timings)
+    return res
 
 
 if __name__ == "__main__":

@@ -324,6 +324,12 @@ SYMBOLS = {
     "hrv_lpips_head_f32": (C.c_int, [C.POINTER(hrv_lpips_tap_t), _i32, _i32, _vp, _vp]),
     "hrv_pool3x3_nhwc_f32": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp]),
     "hrv_inception_head_f32": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "hrv_fid_prep_u8": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "hrv_inception_pool_f32": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "hrv_gemm_nt_f64": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i64, _i64, _i32, C.c_double, _i32, _vp, _i64, _vp]),
+    "hrv_feat_mean_f64": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
+    "hrv_feat_center_t_f64": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp]),
+    "hrv_kid_subset_sums_f64": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),
     "hrv_seg_iou_nchw_f32": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "hrv_lpips_prep_resize_nchw_f32": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_float),
                                                  C.POINTER(C.c_float), _vp, _vp]),

@@ -1,8 +1,11 @@
-// Inception-v3 pieces of evaluate.py's Inception Score on gfx950 (fp32) that are not convolutions:
-//   - the two 3x3 pools of the network over NHWC channel slices: max, stride 2, no padding (the stem and the grid reductions
+// Inception-v3 pieces of evaluate.py's Inception Score and FID / KID on gfx950 (fp32) that are not convolutions:
+//   - the 3x3 pools of the network over NHWC channel slices: max, stride 2, no padding (the stem and the grid reductions
 //     Mixed_6a / Mixed_7a, whose pooled branch is written straight into its slice of the block's concatenation), and
-//     average, stride 1, padding 1, count_include_pad (the pooled branch of every other Mixed block);
-//   - the classifier head: mean over the last feature map, fc with bias, softmax.
+//     average, stride 1, padding 1, count_include_pad (the pooled branch of every other Mixed block); the FID variant of the
+//     network pools those branches differently: the same average divided by the taps inside the image, and in Mixed_7c a
+//     max, stride 1, padding 1;
+//   - the FID input: a decoded uint8 image of any size -> fp32 NHWC4 299 x 299 (x / 255, bilinear, 2v - 1) in one pass;
+//   - the classifier head: mean over the last feature map (also on its own: the FID feature), fc with bias, softmax.
 // The 94 convolutions run on the fp32 conv engine (conv_f32.hip) with BatchNorm folded into scale / shift.
 // Every reduction here has a fixed order that does not depend on the batch: the same image gives the same bits on every run
 // and in every batch.
@@ -25,6 +28,12 @@ struct MaxCol {
     v.x = fmaxf(fmaxf(a.x, b.x), c.x); v.y = fmaxf(fmaxf(a.y, b.y), c.y);
     v.z = fmaxf(fmaxf(a.z, b.z), c.z); v.w = fmaxf(fmaxf(a.w, b.w), c.w);
   }
+  // the padded pool: a column starts below every value and takes the rows that exist
+  __device__ __forceinline__ void lowest() { v = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY); }
+  __device__ __forceinline__ void take(const float4* __restrict__ p) {
+    const float4 a = *p;
+    v.x = fmaxf(v.x, a.x); v.y = fmaxf(v.y, a.y); v.z = fmaxf(v.z, a.z); v.w = fmaxf(v.w, a.w);
+  }
   static __device__ __forceinline__ float4 combine(const MaxCol& a, const MaxCol& b, const MaxCol& c) {
     return make_float4(fmaxf(fmaxf(a.v.x, b.v.x), c.v.x), fmaxf(fmaxf(a.v.y, b.v.y), c.v.y),
                        fmaxf(fmaxf(a.v.z, b.v.z), c.v.z), fmaxf(fmaxf(a.v.w, b.v.w), c.v.w));
@@ -44,6 +53,11 @@ struct SumCol {
     return make_float4((float)(((a.x + b.x) + c.x) / 9.0), (float)(((a.y + b.y) + c.y) / 9.0),
                        (float)(((a.z + b.z) + c.z) / 9.0), (float)(((a.w + b.w) + c.w) / 9.0));
   }
+  // count_include_pad=False: `taps` of the nine lie inside the image (4, 6 or 9; 1, 2 or 3 per axis in images narrower than 3)
+  static __device__ __forceinline__ float4 combine(const SumCol& a, const SumCol& b, const SumCol& c, double taps) {
+    return make_float4((float)(((a.x + b.x) + c.x) / taps), (float)(((a.y + b.y) + c.y) / taps),
+                       (float)(((a.z + b.z) + c.z) / taps), (float)(((a.w + b.w) + c.w) / taps));
+  }
 };
 
 struct PoolArgs {
@@ -52,7 +66,9 @@ struct PoolArgs {
   int x_cs, x_co, y_cs, y_co;     // in floats
 };
 
-// MODE 0: max, stride 2, no padding (every tap is inside the image: 2 * (Ho - 1) + 2 <= H - 1).  MODE 1: average, stride 1, padding 1.
+// MODE 0: max, stride 2, no padding (every tap is inside the image: 2 * (Ho - 1) + 2 <= H - 1).  MODE 1: average, stride 1, padding 1,
+// divided by 9.  MODE 2: that average divided by the taps inside the image.  MODE 3: max, stride 1, padding 1, over the taps inside
+// the image (the centre tap always is).
 template <int MODE>
 __global__ __launch_bounds__(256) void pool3x3_kernel(PoolArgs a) {
   constexpr int ST = MODE == 0 ? 2 : 1, PAD = MODE == 0 ? 0 : 1;
@@ -78,6 +94,22 @@ __global__ __launch_bounds__(256) void pool3x3_kernel(PoolArgs a) {
         if (k >= 0 && (k & 1) == 0) *(float4*)(yout + (int64_t)(wo0 + (k >> 1)) * a.y_cs) = MaxCol::combine(p2, p1, cur);
         p2 = p1; p1 = cur;
       }
+    } else if constexpr (MODE == 3) {
+      MaxCol p2, p1, cur;
+      p2.lowest(); p1.lowest();
+      for (int wi = wi0; wi < wi1; ++wi) {
+        cur.lowest();
+        if (wi >= 0 && wi < a.W) {
+#pragma unroll
+          for (int dy = 0; dy < 3; ++dy) {
+            const int hi = hi0 + dy;
+            if (hi >= 0 && hi < a.H) cur.take((const float4*)(xin + ((int64_t)hi * a.W + wi) * a.x_cs));
+          }
+        }
+        const int k = wi - wi0 - 2;
+        if (k >= 0) *(float4*)(yout + (int64_t)(wo0 + k) * a.y_cs) = MaxCol::combine(p2, p1, cur);
+        p2 = p1; p1 = cur;
+      }
     } else {
       SumCol p2, p1, cur;
       p2.zero(); p1.zero();
@@ -91,7 +123,15 @@ __global__ __launch_bounds__(256) void pool3x3_kernel(PoolArgs a) {
           }
         }
         const int k = wi - wi0 - 2;
-        if (k >= 0) *(float4*)(yout + (int64_t)(wo0 + k) * a.y_cs) = SumCol::combine(p2, p1, cur);
+        if constexpr (MODE == 1) {
+          if (k >= 0) *(float4*)(yout + (int64_t)(wo0 + k) * a.y_cs) = SumCol::combine(p2, p1, cur);
+        } else {
+          if (k >= 0) {
+            const int wo = wo0 + k;      // window columns wo - 1 .. wo + 1, rows hi0 .. hi0 + 2
+            const int nw = min(wo + 1, a.W - 1) - max(wo - 1, 0) + 1, nh = min(hi0 + 2, a.H - 1) - max(hi0, 0) + 1;
+            *(float4*)(yout + (int64_t)wo * a.y_cs) = SumCol::combine(p2, p1, cur, (double)(nw * nh));
+          }
+        }
         p2 = p1; p1 = cur;
       }
     }
@@ -113,6 +153,40 @@ __global__ __launch_bounds__(256) void incep_mean_kernel(const float* __restrict
   }
   const float d = (float)HW;
   pooled[i] = make_float4(s.x / d, s.y / d, s.z / d, s.w / d);
+}
+
+// ---------------------------------------------------------------- FID input
+// One thread per output pixel: pytorch-fid's F.interpolate(x / 255, (Ho, Wo), mode='bilinear', align_corners=False) followed by
+// 2v - 1, from the uint8 image as decoded.  Source coordinate max(0, (o + 0.5) * in / out - 0.5), upper neighbour clamped to the last
+// row / column.  The arithmetic is double on the integer pixel values, in the form p + t * (q - p): a constant image comes out
+// exactly, and every output is rounded to fp32 once.  (2v - 1 on v = u / 255 is (2u - 255) / 255.)
+__global__ __launch_bounds__(256) void fid_prep_u8_kernel(const uint8_t* __restrict__ rgb, int N, int H, int W, int Ho, int Wo,
+                                                         float4* __restrict__ out) {
+  const int64_t total = (int64_t)N * Ho * Wo;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int wo = (int)(i % Wo);
+    const int ho = (int)((i / Wo) % Ho);
+    const int n = (int)(i / ((int64_t)Wo * Ho));
+    const double sy = fmax(0.0, ((double)ho + 0.5) * (double)H / (double)Ho - 0.5);
+    const double sx = fmax(0.0, ((double)wo + 0.5) * (double)W / (double)Wo - 0.5);
+    const int y0 = min((int)sy, H - 1), x0 = min((int)sx, W - 1);
+    const int y1 = min(y0 + 1, H - 1), x1 = min(x0 + 1, W - 1);
+    const double ty = sy - (double)y0, tx = sx - (double)x0;
+    const uint8_t* img = rgb + (int64_t)n * H * W * 3;
+    const uint8_t* p00 = img + ((int64_t)y0 * W + x0) * 3;
+    const uint8_t* p01 = img + ((int64_t)y0 * W + x1) * 3;
+    const uint8_t* p10 = img + ((int64_t)y1 * W + x0) * 3;
+    const uint8_t* p11 = img + ((int64_t)y1 * W + x1) * 3;
+    float v[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const double a = (double)p00[c], b = (double)p01[c], d = (double)p10[c], e = (double)p11[c];
+      const double top = a + tx * (b - a), bot = d + tx * (e - d);
+      const double u = top + ty * (bot - top);
+      v[c] = (float)((2.0 * u - 255.0) / 255.0);
+    }
+    out[i] = make_float4(v[0], v[1], v[2], 0.f);
+  }
 }
 
 __device__ __forceinline__ float wave_sum64(float v) {
@@ -197,8 +271,10 @@ using namespace hrv;
 extern "C" int hrv_pool3x3_nhwc_f32(const float* x, int32_t N, int32_t H, int32_t W, int32_t C, int32_t x_cstride, int32_t x_coff,
                                     int32_t mode, float* y, int32_t y_cstride, int32_t y_coff, hrv_stream_t stream) {
   HRV_REQUIRE(x && y && N > 0 && H > 0 && W > 0 && C > 0, "pool3x3: bad args");
-  HRV_REQUIRE(mode == 0 || mode == 1, "pool3x3: mode %d (0: max stride 2, 1: average stride 1 pad 1)", mode);
-  HRV_REQUIRE(mode == 1 || (H >= 3 && W >= 3), "pool3x3: max-pool input %dx%d is smaller than the window", H, W);
+  HRV_REQUIRE(mode >= 0 && mode <= 3,
+              "pool3x3: mode %d (0: max stride 2, 1: average stride 1 pad 1, 2: that average over the taps inside, 3: max stride 1 pad 1)",
+              mode);
+  HRV_REQUIRE(mode != 0 || (H >= 3 && W >= 3), "pool3x3: max-pool input %dx%d is smaller than the window", H, W);
   HRV_REQUIRE(C % 4 == 0 && x_cstride % 4 == 0 && x_coff % 4 == 0 && y_cstride % 4 == 0 && y_coff % 4 == 0 && x_coff >= 0 &&
                   y_coff >= 0 && x_coff + C <= x_cstride && y_coff + C <= y_cstride,
               "pool3x3: channels C=%d, slices (%d of %d, %d of %d) must be multiples of 4 and in range", C, x_coff, x_cstride, y_coff,
@@ -212,8 +288,31 @@ extern "C" int hrv_pool3x3_nhwc_f32(const float* x, int32_t N, int32_t H, int32_
   a.x_cs = x_cstride; a.x_co = x_coff; a.y_cs = y_cstride; a.y_co = y_coff;
   const int grid = grid_for((int64_t)N * a.Ho * a.strips * a.C4);
   if (mode == 0) hipLaunchKernelGGL(pool3x3_kernel<0>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(pool3x3_kernel<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+  else if (mode == 1) hipLaunchKernelGGL(pool3x3_kernel<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+  else if (mode == 2) hipLaunchKernelGGL(pool3x3_kernel<2>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(pool3x3_kernel<3>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
   return check_launch("pool3x3_kernel");
+}
+
+extern "C" int hrv_fid_prep_u8(const uint8_t* rgb, int32_t N, int32_t H, int32_t W, int32_t Ho, int32_t Wo, float* out,
+                               hrv_stream_t stream) {
+  HRV_REQUIRE(rgb && out && N > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0, "fid_prep_u8: bad args");
+  HRV_REQUIRE(((uintptr_t)out & 15) == 0, "fid_prep_u8: 16-byte alignment");
+  hipLaunchKernelGGL(fid_prep_u8_kernel, dim3(grid_for((int64_t)N * Ho * Wo)), dim3(256), 0, (hipStream_t)stream, rgb, N, H, W, Ho, Wo,
+                     (float4*)out);
+  return check_launch("fid_prep_u8_kernel");
+}
+
+extern "C" int hrv_inception_pool_f32(const float* feat, int32_t N, int32_t HW, int32_t C, int32_t cstride, float* pooled,
+                                      hrv_stream_t stream) {
+  HRV_REQUIRE(feat && pooled && N > 0 && HW > 0, "inception_pool: bad args");
+  HRV_REQUIRE(C > 0 && C % 4 == 0 && cstride % 4 == 0 && cstride >= C, "inception_pool: C=%d cstride=%d must be multiples of 4", C,
+              cstride);
+  HRV_REQUIRE((((uintptr_t)feat | (uintptr_t)pooled) & 15) == 0, "inception_pool: 16-byte alignment");
+  HRV_REQUIRE((int64_t)N * C < ((int64_t)1 << 31), "inception_pool: batch too large");
+  hipLaunchKernelGGL(incep_mean_kernel, dim3((N * (C / 4) + 255) / 256), dim3(256), 0, (hipStream_t)stream, feat, N, HW, C / 4,
+                     cstride, (float4*)pooled);
+  return check_launch("incep_mean_kernel");
 }
 
 extern "C" int hrv_inception_head_f32(const float* feat, int32_t N, int32_t HW, int32_t C, int32_t cstride, const float* fc_w,

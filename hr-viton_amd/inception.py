@@ -11,6 +11,10 @@ Forward: the input kernel (uint8 NHWC -> fp32, ToTensor + Normalize(0.5, 0.5)) -
 folded into the engine's per-channel scale / shift on the host in float64, ReLU in its epilogue, every branch written at its channel
 offset of the block's output (no concatenation pass) -> the 3x3 pools and the head of csrc/inception.hip (mean over the last map, fc,
 softmax).  No autograd, no training mode, no CPU path.
+
+``FIDInceptionV3`` is the network behind pytorch-fid and torch-fidelity (``pt_inception-2015-12-05-6726825d.pth``): the same units
+under the same names, no ``AuxLogits``, ``fc`` [1008, 2048], and other 3x3 pools in the pooled branch of four block types
+(``FID_POOLS``).  It is the same plan, stem and block runner over that table; ``features_u8`` gives the 2048-wide pooled vector.
 """
 from __future__ import annotations
 
@@ -54,7 +58,8 @@ class BasicConv2d(nn.Module):
 # The blocks as data: per block type the branches in torch.cat order; a branch is a chain of steps:
 #   "name"                   one BasicConv2d, input = the previous step's output (the block input for the first step)
 #   ("name_a", "name_b")     two units over the SAME input whose outputs are concatenated (Mixed_7b/7c's 1x3 | 3x1 pairs)
-#   "avg" / "max"            the 3x3 pool of the block input (average: stride 1, padding 1; max: stride 2)
+#   "avg" / "max"            the 3x3 pool of the block input (average: stride 1, padding 1; max: stride 2); a network variant may
+#                            name another pool step of POOL_MODES for a block's "avg" (FID_POOLS)
 # and per unit (out channels or a key into the block's constructor arguments, kernel, stride, padding (h, w)).
 _A = {"branches": [["branch1x1"], ["branch5x5_1", "branch5x5_2"], ["branch3x3dbl_1", "branch3x3dbl_2", "branch3x3dbl_3"],
                    ["avg", "branch_pool"]],
@@ -81,6 +86,10 @@ _E = {"branches": [["branch1x1"], ["branch3x3_1", ("branch3x3_2a", "branch3x3_2b
                 "branch3x3dbl_3a": (384, (1, 3), 1, (0, 1)), "branch3x3dbl_3b": (384, (3, 1), 1, (1, 0)),
                 "branch_pool": (192, 1, 1, 0)}}
 _TYPES = {"A": _A, "B": _B, "C": _C, "D": _D, "E": _E}
+# pool step -> mode of hrv_pool3x3_nhwc_f32.  "avg_inside": the stride-1 average divided by the taps inside the image
+# (count_include_pad=False); "max_same": max, stride 1, padding 1.
+POOL_MODES = {"max": 0, "avg": 1, "avg_inside": 2, "max_same": 3}
+POOL_LABELS = {0: "maxpool3x3s2", 1: "avgpool3x3s1", 2: "avgpool3x3s1_inside", 3: "maxpool3x3s1"}
 
 # the stem: (name, in, out, kernel, stride, padding) or "max"
 STEM = [("Conv2d_1a_3x3", 3, 32, 3, 2, 0), ("Conv2d_2a_3x3", 32, 32, 3, 1, 0), ("Conv2d_2b_3x3", 32, 64, 3, 1, 1), "max",
@@ -91,6 +100,13 @@ MIXED = [("Mixed_5b", "A", 192, {"pf": 32}), ("Mixed_5c", "A", 256, {"pf": 64}),
          ("Mixed_6b", "C", 768, {"c7": 128}), ("Mixed_6c", "C", 768, {"c7": 160}), ("Mixed_6d", "C", 768, {"c7": 160}),
          ("Mixed_6e", "C", 768, {"c7": 192}),
          ("Mixed_7a", "D", 768, {}), ("Mixed_7b", "E", 1280, {}), ("Mixed_7c", "E", 2048, {})]
+# The FID network (pytorch-fid's FIDInceptionA / C / E_1 / E_2): the pool step that stands for "avg" in the pooled branch, per block.
+# Mixed_6a, Mixed_7a and the stem keep torchvision's pools.
+FID_POOLS = {"Mixed_5b": "avg_inside", "Mixed_5c": "avg_inside", "Mixed_5d": "avg_inside",
+             "Mixed_6b": "avg_inside", "Mixed_6c": "avg_inside", "Mixed_6d": "avg_inside", "Mixed_6e": "avg_inside",
+             "Mixed_7b": "avg_inside", "Mixed_7c": "max_same"}
+FID_NUM_CLASSES = 1008
+FID_SIZE = 299
 
 
 def _step_names(step) -> Tuple[str, ...]:
@@ -100,16 +116,17 @@ def _step_names(step) -> Tuple[str, ...]:
 class InceptionBlock(nn.Module):
     """One Mixed_* block: the BasicConv2d children of torchvision's InceptionA..E under their names."""
 
-    def __init__(self, kind: str, cin: int, args: Dict[str, int]):
+    def __init__(self, kind: str, cin: int, args: Dict[str, int], pool: Optional[str] = None):
         super().__init__()
         spec = _TYPES[kind]
         self.kind, self.cin = kind, cin
-        self.branches = spec["branches"]
+        assert pool is None or pool in POOL_MODES, pool
+        self.branches = spec["branches"] if pool is None else [[pool if st == "avg" else st for st in br] for br in spec["branches"]]
         self.widths: List[int] = []        # output channels per branch, in cat order
         for br in self.branches:
             c = cin
             for step in br:
-                if step in ("avg", "max"):
+                if isinstance(step, str) and step in POOL_MODES:
                     continue
                 outs = 0
                 for nm in _step_names(step):
@@ -130,8 +147,9 @@ class InceptionBlock(nn.Module):
 
 
 def pool3x3(a: Act, mode: int, out: Optional[Act] = None) -> Act:
-    """hrv_pool3x3_nhwc_f32 over a channel slice: mode 0 max stride 2 (no padding), mode 1 average stride 1 padding 1 (/ 9)."""
-    assert not a.bf16 and a.C % 4 == 0, (a.C, a.t.dtype)
+    """hrv_pool3x3_nhwc_f32 over a channel slice: mode 0 max stride 2 (no padding), mode 1 average stride 1 padding 1 (/ 9), mode 2
+    that average divided by the taps inside the image, mode 3 max stride 1 padding 1."""
+    assert not a.bf16 and a.C % 4 == 0 and mode in POOL_LABELS, (a.C, a.t.dtype, mode)
     Ho, Wo = ((a.H - 3) // 2 + 1, (a.W - 3) // 2 + 1) if mode == 0 else (a.H, a.W)
     if Ho < 1 or Wo < 1:
         raise ValueError(f"Inception3: max-pool input {a.H}x{a.W} is smaller than its 3x3 window")
@@ -139,7 +157,7 @@ def pool3x3(a: Act, mode: int, out: Optional[Act] = None) -> Act:
         out = Act(torch.empty((a.N, Ho, Wo, a.C), dtype=torch.float32, device=a.t.device), a.C, 0)
     assert (out.N, out.H, out.W, out.C) == (a.N, Ho, Wo, a.C) and not out.bf16, (out.t.shape, out.C)
     lib = _lib.load()
-    with ops._Timed("pool", "maxpool3x3s2" if mode == 0 else "avgpool3x3s1", 0.0, ops.act_bytes(a) + ops.act_bytes(out),
+    with ops._Timed("pool", POOL_LABELS[mode], 0.0, ops.act_bytes(a) + ops.act_bytes(out),
                     "pool3x3_kernel"):
         _lib.check(lib.hrv_pool3x3_nhwc_f32(a.t.data_ptr(), a.N, a.H, a.W, a.C, a.cstride, a.coff, mode, out.t.data_ptr(), out.cstride,
                                             out.coff, _stream()), "hrv_pool3x3_nhwc_f32")
@@ -149,6 +167,9 @@ def pool3x3(a: Act, mode: int, out: Optional[Act] = None) -> Act:
 class Inception3(nn.Module):
     """torchvision.models.inception.Inception3 in eval mode on the HIP path.  ``forward(x)``: fp32 NCHW [N,3,H,W] CUDA -> logits
     [N,1000]; ``forward_u8(img)``: uint8 [N,H,W,3] CUDA as decoded -> softmax probabilities [N,1000]."""
+
+    STATE_DICT_OF = "torchvision inception_v3().state_dict()"
+    POOLS: Dict[str, str] = {}      # block name -> the pool step that replaces "avg" (a variant's table; torchvision: none)
 
     def __init__(self, num_classes: int = NUM_CLASSES, aux_logits: bool = True, transform_input: bool = False):
         super().__init__()
@@ -160,7 +181,7 @@ class Inception3(nn.Module):
                 nm, cin, cout, k, s, p = st
                 setattr(self, nm, BasicConv2d(cin, cout, k, s, p))
         for nm, kind, cin, args in MIXED:
-            setattr(self, nm, InceptionBlock(kind, cin, args))
+            setattr(self, nm, InceptionBlock(kind, cin, args, self.POOLS.get(nm)))
         self.fc = nn.Linear(2048, num_classes)
         nn.init.normal_(self.fc.weight, std=FC_INIT_GAIN / 2048 ** 0.5)      # (random initialisation: logits that tell images apart)
         nn.init.zeros_(self.fc.bias)
@@ -182,7 +203,7 @@ class Inception3(nn.Module):
         sd = {k: v for k, v in state_dict.items() if not k.startswith("AuxLogits.")}
         for k in self.state_dict().keys():
             if k not in sd and not k.endswith("num_batches_tracked"):
-                raise KeyError(f"Inception3.load_state_dict: {k} missing (expected torchvision inception_v3().state_dict())")
+                raise KeyError(f"{type(self).__name__}.load_state_dict: {k} missing (expected {self.STATE_DICT_OF})")
         res = super().load_state_dict(sd, strict=strict, **kw)
         self._plan = None
         return res
@@ -219,13 +240,13 @@ class Inception3(nn.Module):
             cur = x
             for i, step in enumerate(br):
                 last = i == len(br) - 1
-                if step in ("avg", "max"):
+                if isinstance(step, str) and step in POOL_MODES:
                     if last:        # Mixed_6a / Mixed_7a: the pooled input is the branch
                         if out is None:
                             out = self._block_out(blk, x, convs, name)
-                        cur = pool3x3(x, 0 if step == "max" else 1, out.slice(off, width))
+                        cur = pool3x3(x, POOL_MODES[step], out.slice(off, width))
                     else:
-                        cur = pool3x3(x, 0 if step == "max" else 1)
+                        cur = pool3x3(x, POOL_MODES[step])
                     continue
                 names = _step_names(step)
                 if last and out is None:
@@ -298,6 +319,20 @@ class Inception3(nn.Module):
                                                   _stream()), "hrv_inception_head_f32")
         return logits, probs
 
+    def pooled(self, f: Act, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The mean over H x W of the last feature map, fp32 [N, C], in the head's fixed pixel order (the head's first stage on its
+        own).  ``out``: a contiguous fp32 [N, C] CUDA tensor to write into, e.g. rows of a feature bank."""
+        assert f.coff == 0 and not f.bf16, (f.coff, f.t.dtype)
+        if out is None:
+            out = torch.empty((f.N, f.C), dtype=torch.float32, device=f.t.device)
+        if out.shape != (f.N, f.C) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != f.t.device:
+            raise HrvError(f"{type(self).__name__}.pooled: out must be a contiguous fp32 [{f.N}, {f.C}] tensor on {f.t.device}")
+        lib = _lib.load()
+        with ops._Timed("head", "inception_pool", 0.0, ops.act_bytes(f), "incep_mean_kernel"):
+            _lib.check(lib.hrv_inception_pool_f32(f.t.data_ptr(), f.N, f.H * f.W, f.C, f.cstride, out.data_ptr(), _stream()),
+                       "hrv_inception_pool_f32")
+        return out
+
     def _check_mode(self):
         if self.training:
             raise NotImplementedError("Inception3: evaluation only on the HIP path (call .eval())")
@@ -325,6 +360,33 @@ class Inception3(nn.Module):
             _lib.check(lib.hrv_lpips_prep_u8(img.contiguous().data_ptr(), N, H, W, _ZERO3, _ONE3, x.data_ptr(), _stream()),
                        "hrv_lpips_prep_u8")
             return self.head(self.features(Act(x, 3)), True)[1]
+
+
+class FIDInceptionV3(Inception3):
+    """pytorch-fid's / torch-fidelity's FID Inception-v3 (``pt_inception-2015-12-05-6726825d.pth``) on the HIP path: ``Inception3``'s
+    plan, stem and block runner over ``FID_POOLS``.  ``fc`` ([1008, 2048]) belongs to the state dict and is never run: the metric
+    reads the pooled 2048-wide vector.  ``features_u8(img)``: uint8 [N,H,W,3] CUDA of any size -> fp32 [N, 2048]."""
+
+    STATE_DICT_OF = "the FID Inception-v3 state dict, pt_inception-2015-12-05-6726825d.pth"
+    POOLS = FID_POOLS
+
+    def __init__(self):
+        super().__init__(num_classes=FID_NUM_CLASSES, aux_logits=False, transform_input=False)
+
+    def features_u8(self, img: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """img: uint8 [N,H,W,3] CUDA images as decoded, any size.  The input kernel resizes to 299x299 as pytorch-fid does
+        (x / 255, bilinear with align_corners=False on the full-size image, 2v - 1); returns the mean over the last 8x8 map, fp32
+        [N, 2048] (into ``out`` when given)."""
+        self._check_mode()
+        if not isinstance(img, torch.Tensor) or not img.is_cuda or img.dtype != torch.uint8 or img.dim() != 4 or img.shape[3] != 3:
+            raise HrvError("FIDInceptionV3: expected uint8 CUDA images [N,H,W,3]")
+        N, H, W, _ = img.shape
+        with torch.no_grad():
+            x = torch.empty((N, FID_SIZE, FID_SIZE, 4), dtype=torch.float32, device=img.device)
+            lib = _lib.load()
+            _lib.check(lib.hrv_fid_prep_u8(img.contiguous().data_ptr(), N, H, W, FID_SIZE, FID_SIZE, x.data_ptr(), _stream()),
+                       "hrv_fid_prep_u8")
+            return self.pooled(self.features(Act(x, 3)), out)
 
 
 _ZERO3 = (C.c_float * 3)(0.0, 0.0, 0.0)

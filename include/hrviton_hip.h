@@ -916,10 +916,12 @@ typedef struct {
 int hrv_lpips_head_f32(const hrv_lpips_tap_t* taps, int32_t ntaps, int32_t B, float* out, hrv_stream_t stream);
 
 /* ---- Inception-v3 (evaluate.py's Inception Score; inception.hip).  The convolutions run on hrv_conv2d_nhwc_f32. ---- */
-/* The network's two 3x3 pools over channels [coff, coff + C) of NHWC fp32 tensors (C, cstride, coff multiples of 4), so a pool reads
+/* The network's 3x3 pools over channels [coff, coff + C) of NHWC fp32 tensors (C, cstride, coff multiples of 4), so a pool reads
  * a slice and writes a slice of a concatenation.  mode 0: max, stride 2, no padding, floor -> [N,(H-3)/2+1,(W-3)/2+1,C] (exact);
  * mode 1: average, stride 1, padding 1, always divided by 9 (F.avg_pool2d's count_include_pad=True) -> [N,H,W,C], the nine values
- * added in double and rounded once.  Channels of `y` outside the slice are not touched.  x and y must not overlap. */
+ * added in double and rounded once; mode 2: the same sum divided by the number of taps inside the image (count_include_pad=False:
+ * 4, 6 or 9); mode 3: max, stride 1, padding 1 -> [N,H,W,C], padding never wins (exact).  Modes 2 and 3 are the pooled branches of
+ * the FID variant of the network.  Channels of `y` outside the slice are not touched.  x and y must not overlap. */
 int hrv_pool3x3_nhwc_f32(const float* x, int32_t N, int32_t H, int32_t W, int32_t C, int32_t x_cstride, int32_t x_coff, int32_t mode,
                          float* y, int32_t y_cstride, int32_t y_coff, hrv_stream_t stream);
 /* The classifier head over the last feature map feat [N,HW,cstride] (channels [0, C)): pooled[n][c] = mean over the HW pixels
@@ -928,6 +930,33 @@ int hrv_pool3x3_nhwc_f32(const float* x, int32_t N, int32_t H, int32_t W, int32_
  * in every batch and on every run. */
 int hrv_inception_head_f32(const float* feat, int32_t N, int32_t HW, int32_t C, int32_t cstride, const float* fc_w, const float* fc_b,
                            int32_t K, float* pooled, float* logits, float* probs, hrv_stream_t stream);
+
+/* The FID input in one pass (pytorch-fid's F.interpolate(x / 255, size=(Ho, Wo), mode='bilinear', align_corners=False), then 2v - 1):
+ * uint8 [N,H,W,3] of any size -> fp32 NHWC [N,Ho,Wo,4], channel 3 zero.  Source coordinate max(0, (o + 0.5) * in / out - 0.5), upper
+ * neighbour clamped to the last row / column, no antialiasing; evaluated in double on the pixel values and rounded to fp32 once (a
+ * constant image c gives exactly the fp32 nearest to 2c/255 - 1). */
+int hrv_fid_prep_u8(const uint8_t* rgb, int32_t N, int32_t H, int32_t W, int32_t Ho, int32_t Wo, float* out, hrv_stream_t stream);
+/* The first stage of the head on its own: pooled[n][c] = mean over the HW pixels of feat [N,HW,cstride] (channels [0, C)), in pixel
+ * order, fp32 [N,C] -- the 2048-wide FID feature.  The same bits as the head's workspace. */
+int hrv_inception_pool_f32(const float* feat, int32_t N, int32_t HW, int32_t C, int32_t cstride, float* pooled, hrv_stream_t stream);
+
+/* ---- feature statistics of FID / KID in float64 on the matrix cores (feat_stats.hip) ---- */
+/* C[i][j] = epi(sum_k A[i][k] * B[j][k]), i < M, j < N: A [M][lda], B [N][ldb] row-major with k contiguous, both fp32
+ * (operands_f64 == 0) or both fp64; products and sums in fp64 on v_mfma_f64_16x16x4_f64 in ascending k; C fp64 [M][ldc].  No atomics,
+ * no split-K: an element does not depend on the grid.  Any M, N, K >= 1.  epilogue 0 (linear): s * param; 1 (poly3):
+ * t = s / param + 1, (t * t) * t -- KID's polynomial kernel with param = the feature width.  symmetric != 0 (needs B == A, N == M):
+ * only tiles on and above the diagonal are computed and each element is written to (i, j) and (j, i), so C is bitwise symmetric. */
+int hrv_gemm_nt_f64(const void* A, const void* B, int32_t operands_f64, int32_t M, int32_t N, int32_t K, int64_t lda, int64_t ldb,
+                    int32_t epilogue, double param, int32_t symmetric, double* C, int64_t ldc, hrv_stream_t stream);
+/* mean[c] = (sum over the n rows of x fp32 [n][D], in row order, in fp64) / n */
+int hrv_feat_mean_f64(const float* x, int32_t n, int32_t D, double* mean, hrv_stream_t stream);
+/* xt fp64 [D][n]: xt[c][r] = (double)x[r][c] - mean[c] */
+int hrv_feat_center_t_f64(const float* x, const double* mean, int32_t n, int32_t D, double* xt, hrv_stream_t stream);
+/* KID's subset sums: Kxx fp64 [nx][nx], Kyy [ny][ny], Kxy [nx][ny] (dense), ix / iy int32 [S][m] device arrays of row numbers
+ * (unsorted, no repeats; an index outside its matrix is not read and turns the sum into NaN).  out fp64 [S][3] = (sum of
+ * Kxx[ix,ix] off the diagonal, sum of Kyy[iy,iy] off the diagonal, sum of Kxy[ix,iy]), gathered and added in a fixed order. */
+int hrv_kid_subset_sums_f64(const double* Kxx, int32_t nx, const double* Kyy, int32_t ny, const double* Kxy, const int32_t* ix,
+                            const int32_t* iy, int32_t S, int32_t m, double* out, hrv_stream_t stream);
 
 /* ---- validation passes of the training scripts (validate.hip) ---- */
 /* The counts behind train_condition.py's iou_metric (:18-36), per sample, in one launch: seg fp32 NCHW [N,13,h,w] (raw logits), cm

@@ -15,6 +15,11 @@
    (``forward_resized``: one launch for both resizes and ScalingLayers) against the unfused one (``forward`` of two
    ``glue.resize_nchw`` results: four launches and a round trip), batch 1 and B, whole call and front end alone; and the IoU count
    kernel at 8 x 256 x 192 and 4 x 1024 x 768 as bytes (108 per pixel) over event time.
+6. FID / KID (``evaluate.py --fid``): the FID Inception-v3's pooled features per image from decoded 1024x768 uint8 images (input
+   kernel with the 299x299 resize, 94 convolutions, pools, mean), batch 1 and B, on seeded random weights; and the statistics over
+   feature banks of 2032 x 2048 (the size of a VITON-HD test set): ``moments`` (mean, centre-and-transpose, the symmetric fp64
+   covariance GEMM: 2 x 2048^2 x 2032 / 2 FLOPs computed), one ``poly_gram`` of 2032 x 2032 x 2048, both as TFLOP/s of fp64 over
+   event time, KID's subset sums for 100 subsets of 1000, and the host's Frechet distance (two 2048 x 2048 ``eigh``) in wall time.
 Event times include launch gaps; for kernel-only times run this under ``rocprofv3 --kernel-trace --stats`` in a run of its own.
 Prints one JSON line.
 """
@@ -85,6 +90,40 @@ def inception_bench(B, reps):
                              "conv_gflop_per_image": flops / b / 1e9, "conv_event_ms": ms,
                              "conv_tflops_over_event_time": flops / (ms * 1e-3) / 1e12 if ms > 0 else None,
                              "tflops_over_wall": flops / t / 1e12}
+    return out
+
+
+def fid_bench(B, reps, n=2032, D=2048):
+    from hr_viton_amd import feat_stats
+    from hr_viton_amd.inception import FIDInceptionV3
+    torch.manual_seed(0)
+    net = FIDInceptionV3().eval()
+    g = torch.Generator(device="cuda").manual_seed(3)
+    out = {"features_1024x768": {}}
+    for b in sorted({1, B}):
+        img = torch.randint(0, 256, (b, 1024, 768, 3), dtype=torch.uint8, device="cuda", generator=g)
+        out["features_1024x768"][f"batch_{b}"] = {"us_per_image": 1e6 * timed(lambda: net.features_u8(img), reps) / b}
+    del net
+    fp = torch.randn(n, D, device="cuda", generator=g).abs_()
+    fg = torch.randn(n, D, device="cuda", generator=g).abs_() * 1.1
+    r = max(2, reps // 4)
+    t_m = timed(lambda: feat_stats.moments(fp), r)
+    t_g = timed(lambda: feat_stats.poly_gram(fp, fg), r)
+    t_gs = timed(lambda: feat_stats.poly_gram(fp, fp), r)
+    ix, iy = feat_stats.kid_subsets(n, n, 1000, 100)
+    kxx, kyy, kxy = feat_stats.poly_gram(fp, fp), feat_stats.poly_gram(fg, fg), feat_stats.poly_gram(fp, fg)
+    ixd, iyd = torch.from_numpy(ix).cuda(), torch.from_numpy(iy).cuda()
+    t_k = timed(lambda: feat_stats.kid_subset_sums(kxx, kyy, kxy, ixd, iyd), r)
+    (mu1, s1), (mu2, s2) = feat_stats.moments(fp), feat_stats.moments(fg)
+    t0 = time.perf_counter()
+    fid = feat_stats.frechet_distance(mu1, s1, mu2, s2)
+    t_f = time.perf_counter() - t0
+    tri = (D // 64) * (D // 64 + 1) // 2 * 64 * 64          # elements of the computed triangle of 64 x 64 tiles
+    out["stats_%dx%d" % (n, D)] = {
+        "moments_ms": 1e3 * t_m, "moments_tflops_f64": 2.0 * tri * n / t_m / 1e12,
+        "poly_gram_ms": 1e3 * t_g, "poly_gram_tflops_f64": 2.0 * n * n * D / t_g / 1e12,
+        "poly_gram_symmetric_ms": 1e3 * t_gs, "kid_subset_sums_100x1000_ms": 1e3 * t_k,
+        "frechet_distance_host_s": t_f, "fid_of_the_synthetic_banks": fid}
     return out
 
 
@@ -176,7 +215,7 @@ def main():
                           "byte_floor_ms_per_pair": 1e3 * fb / B, "valu_floor_ms_per_pair": 1e3 * ff / B,
                           "fraction_of_floor": floor / t_ps},
            "lpips_128": {"B": B, "ms_per_pair": 1e3 * t_lp / B},
-           "inception_299": inception_bench(B, a.reps), "validation": validation_bench(B, a.reps)}
+           "inception_299": inception_bench(B, a.reps), "validation": validation_bench(B, a.reps), "fid": fid_bench(B, a.reps)}
     if a.e2e:
         res["evaluate_py"] = e2e(a.e2e, a.workers, B)
     print(json.dumps(res))
