@@ -137,6 +137,21 @@ class hrv_conv2d_t(C.Structure):
                 ("res_mode", C.c_int32), ("mixed_flags", C.c_int32), ("_pad3", C.c_int32)]
 
 
+class hrv_conv2d_wgrad_t(C.Structure):
+    _fields_ = [("dy", C.c_void_p), ("dy_cstride", C.c_int32), ("dy_coff", C.c_int32), ("Cout", C.c_int32), ("x_C", C.c_int32),
+                ("x", C.c_void_p), ("x_cstride", C.c_int32), ("x_coff", C.c_int32), ("x_up_shift", C.c_int32), ("x_C_real", C.c_int32),
+                ("ci_base", C.c_int32), ("CinTot", C.c_int32),
+                ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("Ho", C.c_int32), ("Wo", C.c_int32),
+                ("KH", C.c_int32), ("KW", C.c_int32), ("stride", C.c_int32), ("pad", C.c_int32),
+                ("mma_bf16", C.c_int32), ("storage_flags", C.c_int32), ("_pad", C.c_int32),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64), ("dw_oihw", C.c_void_p), ("dbias", C.c_void_p),
+                ("accumulate", C.c_int32), ("dbias_accumulate", C.c_int32)]
+
+
+# enum hrv_wgrad_route (hrv_conv2d_wgrad_route): the last one + the shape class 0..8
+WGRAD_F32, WGRAD_BF16, WGRAD_S2, WGRAD_TR = 0, 1, 2, 3
+
+
 class hrv_flow_warp_t(C.Structure):
     _fields_ = [("src", C.c_void_p), ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32),
                 ("src_cstride", C.c_int32), ("src_coff", C.c_int32), ("flow", C.c_void_p),
@@ -187,15 +202,8 @@ SYMBOLS = {
                                                 _vp, _i32, _vp, _i32, _i32, _vp, _ip, _vp, _ip]),
     "hrv_conv2d_pack_weight_multi": (C.c_int, [_vp, _vp, _i32, _i32, _vp]),
     "hrv_conv2d_wgrad_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32, _i64]),
-    "hrv_conv2d_wgrad_nhwc_f32": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
-                                            _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _i32,
-                                            _vp, _i32, _vp]),
-    "hrv_conv2d_wgrad_bf16mma_nhwc_f32": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32,
-                                                    _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp,
-                                                    _i64, _vp, _i32, _vp, _i32, _vp]),
-    "hrv_conv2d_wgrad_bf16mma_st_nhwc_f32": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32,
-                                                       _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
-                                                       _vp, _i64, _vp, _i32, _vp, _i32, _i32, _vp]),
+    "hrv_conv2d_wgrad_route": (C.c_int, [C.POINTER(hrv_conv2d_wgrad_t)]),
+    "hrv_conv2d_wgrad": (C.c_int, [C.POINTER(hrv_conv2d_wgrad_t), _vp]),
     "hrv_colsum_nhwc_f32": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _i32, _vp]),
     "hrv_norm_bwd_workspace_elems": (_i64, [_i32, _i32, _i32, _i32]),
     "hrv_spade_norm_bwd2_nhwc_f32": (C.c_int, [C.POINTER(hrv_norm_bwd_t), C.POINTER(hrv_norm_bwd_t), _vp]),
@@ -307,8 +315,6 @@ SYMBOLS = {
     "hrv_instnorm_apply_nhwc_bf16out": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _f, _vp, _i32, _i32, _vp]),
     "hrv_scale_bf16": (C.c_int, [_vp, _i64, _f, _vp, _vp]),
     "hrv_split3_nhwc_bf16": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp]),
-    "hrv_conv2d_wgrad_s2_supported": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32]),
-    "hrv_conv2d_wgrad_tr_supported": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32]),
     "hrv_pad_width_nhwc_bf16": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "hrv_spade_fused_packed_bytes": (C.c_int64, [_i32]),
     "hrv_spade_fused_supported": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32]),

@@ -7,6 +7,7 @@ Nothing here allocates, packs or launches; the entry points run the plan they ge
 docstring names the gate ids of ``conv_dispatch_cases.GATES`` it implements."""
 from __future__ import annotations
 
+import ctypes as C
 import os
 from typing import NamedTuple, Optional, Sequence, Tuple
 
@@ -33,7 +34,8 @@ class Plan(NamedTuple):
     ride: bool = False      # dgrad: ``add_after`` rides in the kernel's epilogue; False with an ``add_after``: an add_slice pass follows
     phases: tuple = ()      # dgrad, stride 2 on the generic engine: (a, b, Hp, Wp, cfg) of every non-empty phase
     pad: str = ""           # wgrad: zero columns appended to dY up to a multiple of 4: "" none, "bf16" pad_width_bf16, "f32" F.pad
-    entry: str = ""         # wgrad: the C entry point
+    desc: object = None     # wgrad: the hrv_conv2d_wgrad_t the route was asked with (wgrad_desc of the unpadded operands); conv_wgrad launches
+                            # with it where dY needs no padding
 
     @property
     def family(self) -> str:
@@ -230,30 +232,10 @@ def _ride_ok(add_after, cin: int) -> bool:
             add_after.coff + (cin + 3) // 4 * 4 <= add_after.cstride and os.environ.get("HRV_DGRAD_ADD_AFTER", "1") != "0")
 
 
-def _wgrad_lds_dma(mb: bool, dy, x, x_up: int, KH: int, KW: int, stride: int, pad: int, H: int, W: int) -> Tuple[str, str]:
-    """(kernel, variant) of the LDS-DMA weight-gradient kernel that will take bf16-stored operands of any width, or ("", "").  Which
-    one runs is the C launch path's own decision (hrv_conv2d_wgrad_{tr,s2}_supported answer from the code that launches: switches,
-    pixel, width and slab-extent limits included), asked here with the conditions wgrad_impl (csrc/conv_bwd.hip) puts in front of
-    each try: edit both places together.
-    Gates: wgrad.tr.* (x_up and storage here, the rest in C), wgrad.s2.*."""
-    if not (mb and dy.bf16 and x.bf16 and x_up == 0):
-        return "", ""
-    lib = _lib.load()
-    N, Ho, Wo, Cout = dy.N, dy.H, dy.W, dy.C
-    if stride == 1 and (Ho, Wo) == (H, W):
-        c = lib.hrv_conv2d_wgrad_tr_supported(Cout, x.Cp, x.cstride, x.coff, dy.cstride, dy.coff, N, H, W, KH, KW, pad)
-        if c > 0:
-            return "conv_wgrad_tr_kernel", f"class {c - 1}"
-    elif (KH, KW, stride, pad) == (4, 4, 2, 2) and (Ho, Wo) == (H // 2 + 1, W // 2 + 1):
-        if lib.hrv_conv2d_wgrad_s2_supported(Cout, x.Cp, x.cstride, x.coff, dy.cstride, dy.coff, N, H, W) > 0:
-            return "conv_wgrad_s2_kernel", ""
-    return "", ""
-
-
 def _wgrad_pad(mb: bool, dy, x, lds_dma: bool) -> str:
     """Zero columns for dY up to the next multiple of 4: the bf16 matrix-core kernel stages quads of 4 pixels of one image row, and
     the columns add nothing to dW or the bias gradient (the X taps they would pair with are never weighted).  "bf16": a dense
-    bf16-stored dY that no LDS-DMA kernel takes (the PatchGAN with bf16 feature maps); "f32": the odd-sized fp32 maps (the
+    bf16-stored dY that no LDS-DMA kernel takes (``lds_dma``: hrv_conv2d_wgrad_route's answer; the PatchGAN with bf16 feature maps); "f32": the odd-sized fp32 maps (the
     PatchGAN's 513 / 257 / 129 columns) instead of the fp32 kernel (60-100 TFLOP/s); "": none.
     Gates: wgrad.pad.bf16.Wo%4, wgrad.pad.f32.Wo%4, wgrad.pad.f32.Wo>=32."""
     if not mb or dy.W % 4 == 0 or dy.coff != 0:
@@ -347,30 +329,54 @@ def plan_dgrad(dy, w, H: int, W: int, stride: int, pad: int, act_mask=None, out=
     return Plan("+".join(kernels), "", 0, o_bf16, mb, False, tuple(phases))
 
 
+def wgrad_desc(dy, x, x_up: int, ci_base: int, cin_tot: int, KH: int, KW: int, stride: int, pad: int,
+               mma_bf16: bool) -> "_lib.hrv_conv2d_wgrad_t":
+    """hrv_conv2d_wgrad's descriptor for these operands, metadata only: what hrv_conv2d_wgrad_route reads.  conv_wgrad adds the
+    pointers and the workspace."""
+    H, W = _hw(x, x_up)
+    return _lib.hrv_conv2d_wgrad_t(
+        dy_cstride=dy.cstride, dy_coff=dy.coff, Cout=dy.C, x_C=x.Cp, x_cstride=x.cstride, x_coff=x.coff, x_up_shift=x_up, x_C_real=x.C,
+        ci_base=ci_base, CinTot=cin_tot, N=dy.N, H=H, W=W, Ho=dy.H, Wo=dy.W, KH=KH, KW=KW, stride=stride, pad=pad,
+        mma_bf16=1 if mma_bf16 else 0, storage_flags=(1 if dy.bf16 else 0) | (2 if x.bf16 else 0))
+
+
 def plan_wgrad(dy, x, x_up: int, ci_base: int, cin_tot: int, KH: int, KW: int, stride: int, pad: int, dw,
                mb: Optional[bool] = None) -> Plan:
-    """The kernel conv_wgrad runs for these operands, the width padding dY gets first and the C entry point: cout1, else
-    hrv_conv2d_wgrad_bf16mma_st_nhwc_f32 for bf16-stored operands (an LDS-DMA kernel where wgrad_impl takes one, else the generic
-    kernel), else the generic kernel on bf16 matrix cores (mixed precision, Wo % 4 == 0 after padding) or in fp32."""
+    """The kernel conv_wgrad runs for these operands and the width padding dY gets first: cout1, else what hrv_conv2d_wgrad_route
+    answers for the descriptor of the UNPADDED operands -- the C function hrv_conv2d_wgrad launches by (wgrad_route,
+    csrc/conv_bwd.hip): an LDS-DMA kernel for bf16-stored operands where one takes the shape, else the generic kernel on bf16
+    matrix cores (mixed precision, Wo % 4 == 0 after padding) or in fp32.
+    Gates, all in C: wgrad.tr.storage, wgrad.tr.x_up (wgrad_route); wgrad.tr.pixels, wgrad.tr.W>=32, wgrad.tr.W>=32.odd,
+    wgrad.tr.x_granule, wgrad.tr.dy_granule, wgrad.tr.Cout%64, wgrad.tr.Cp, wgrad.tr.min_pix_env, wgrad.tr.env (wgrad_tr_class);
+    wgrad.s2.pixels, wgrad.s2.Wo>=32, wgrad.s2.x_granule, wgrad.s2.Cout%128, wgrad.s2.env (wgrad_s2_class)."""
     if mb is None:
         mb = MMA_BF16[0]
-    N, Ho, Wo, Cout = dy.N, dy.H, dy.W, dy.C
-    H, W = _hw(x, x_up)
-    if (Cout == 1 and x_up == 0 and ci_base == 0 and cin_tot == x.C and not dy.bf16 and
-            (Ho, Wo) == (H + 2 * pad - KH + 1, W + 2 * pad - KW + 1) and
-            _cout1_ok(dw, x.bf16, x.C, x.cstride, x.coff, stride, pad, "wgrad")):
-        return Plan(COUT1, mb=mb, entry="hrv_conv_cout1_wgrad_f32")
-    kernel, variant = _wgrad_lds_dma(mb, dy, x, x_up, KH, KW, stride, pad, H, W)
-    route = _wgrad_pad(mb, dy, x, bool(kernel))
-    quads = Wo % 4 == 0 or route != ""          # (after the padding)
-    if x.bf16 or dy.bf16:
-        assert mb and (quads or kernel), "bf16-stored operands need the bf16 matrix-core weight gradient"
-        assert x.bf16, "bf16 dY with an fp32 X is not built"
-        entry = "hrv_conv2d_wgrad_bf16mma_st_nhwc_f32"
-        if not kernel:
-            kernel, variant = "conv_wgrad_kernel", "bf16 stored" if dy.bf16 else "bf16 x-stored"
-    elif mb and quads:      # mixed precision: bf16 matrix cores (needs Wo % 4 == 0: narrow odd-sized maps keep the fp32 kernel)
-        kernel, variant, entry = "conv_wgrad_kernel", "bf16", "hrv_conv2d_wgrad_bf16mma_nhwc_f32"
+    Wo, x_bf16, dy_bf16 = dy.W, x.bf16, dy.bf16
+    if dy.C == 1 and x_up == 0 and ci_base == 0 and cin_tot == x.C and not dy_bf16:
+        H, W = _hw(x, x_up)
+        if ((dy.H, Wo) == (H + 2 * pad - KH + 1, W + 2 * pad - KW + 1) and
+                _cout1_ok(dw, x_bf16, x.C, x.cstride, x.coff, stride, pad, "wgrad")):
+            return Plan(COUT1, mb=mb)
+    d = wgrad_desc(dy, x, x_up, ci_base, cin_tot, KH, KW, stride, pad, mb)
+    route = _lib.load().hrv_conv2d_wgrad_route
+    if x_bf16 or dy_bf16:
+        assert mb, "bf16-stored operands need the bf16 matrix-core weight gradient"
+        assert x_bf16, "bf16 dY with an fp32 X is not built"
+        code = route(C.byref(d))
+        padded = _wgrad_pad(mb, dy, x, code >= _lib.WGRAD_S2)
+        assert Wo % 4 == 0 or padded or code >= _lib.WGRAD_S2, "the generic bf16 matrix-core weight gradient needs Wo % 4 == 0"
+    else:       # mixed precision: bf16 matrix cores (needs Wo % 4 == 0 after the padding: narrow odd-sized maps keep the fp32 kernel)
+        padded = _wgrad_pad(mb, dy, x, False)
+        d.mma_bf16 = 1 if mb and (Wo % 4 == 0 or padded) else 0
+        code = route(C.byref(d))
+    if code < 0:
+        _lib.check(code, "hrv_conv2d_wgrad_route")
+    if code >= _lib.WGRAD_TR:
+        kernel, variant = "conv_wgrad_tr_kernel", f"class {code - _lib.WGRAD_TR}"
+    elif code == _lib.WGRAD_S2:
+        kernel, variant = "conv_wgrad_s2_kernel", ""
+    elif code == _lib.WGRAD_BF16:
+        kernel, variant = "conv_wgrad_kernel", "bf16 stored" if dy_bf16 else ("bf16 x-stored" if x_bf16 else "bf16")
     else:
-        kernel, variant, entry = "conv_wgrad_kernel", "fp32", "hrv_conv2d_wgrad_nhwc_f32"
-    return Plan(kernel, variant, mb=mb, pad=route, entry=entry)
+        kernel, variant = "conv_wgrad_kernel", "fp32"
+    return Plan(kernel, variant, mb=mb, pad=padded, desc=d)

@@ -11,6 +11,7 @@
 #include <string.h>
 
 #include "hrv_common.h"
+#include "wgrad_lds_dma.h"      // (host side only: WgradLdsPlan and the class / launch functions of wgrad_tr.hip, wgrad_s2.hip)
 
 namespace hrv {
 
@@ -964,88 +965,63 @@ extern "C" int64_t hrv_conv2d_wgrad_workspace_bytes(int32_t Cout, int32_t CinTot
   return (S * KH * KW * (int64_t)Cout * CinTot + 256 * (int64_t)Cout) * (int64_t)sizeof(float);   // + bias partials
 }
 
-namespace hrv {
-// wgrad_tr.hip: LDS-DMA + transposing-read weight gradient for bf16-stored operands (1: launched, 0: shape not served)
-int wgrad_tr_try(const void* dy, int dy_cs, int dy_co, int Cout, const void* x, int x_C, int x_cs, int x_co, int x_C_real,
-                 int ci_base, int CinTot, int N, int H, int W, int KH, int KW, int pad, float* workspace,
-                 long long workspace_bytes, float* dbias, int dbias_accumulate, hipStream_t st, int* S_out);
-// wgrad_s2.hip: the same for PatchGAN's 4x4 stride-2 pad-2 layers (1: launched, 0: shape not served)
-int wgrad_s2_try(const void* dy, int dy_cs, int dy_co, int Cout, const void* x, int x_C, int x_cs, int x_co, int x_C_real, int ci_base,
-                 int CinTot, int N, int H, int W, int Ho, int Wo, float* workspace, long long workspace_bytes, float* dbias, hipStream_t st,
-                 int* S_out);
-int wgrad_s2_serves(int Cout, int x_C, int x_cs, int x_co, int dy_cs, int dy_co, int N, int H, int W);
-int wgrad_tr_serves(int dy_cs, int dy_co, int Cout, int x_C, int x_cs, int x_co, int N, int H, int W, int KH, int KW, int pad);
+// Which kernel serves `d`: a hrv_wgrad_route code (HRV_WGRAD_TR + the shape class for conv_wgrad_tr_kernel), or HRV_ERR_ARG for a
+// storage form that is not built.  The ONE place that decides -- hrv_conv2d_wgrad_route answers from it, hrv_conv2d_wgrad launches
+// what it says.  Reads metadata only.  `pl`: the LDS-DMA kernel's class and block geometry where the code is one of theirs.
+// The gates of tests/conv_dispatch_cases.py it implements: wgrad.tr.storage and wgrad.tr.x_up here; wgrad.tr.pixels, wgrad.tr.W>=32,
+// wgrad.tr.W>=32.odd, wgrad.tr.x_granule, wgrad.tr.dy_granule, wgrad.tr.Cout%64, wgrad.tr.Cp, wgrad.tr.min_pix_env, wgrad.tr.env in
+// wgrad_tr_class; wgrad.s2.pixels, wgrad.s2.Wo>=32, wgrad.s2.x_granule, wgrad.s2.Cout%128, wgrad.s2.env in wgrad_s2_class.
+static int wgrad_route(const hrv_conv2d_wgrad_t& d, WgradLdsPlan& pl) {
+  HRV_REQUIRE(d.storage_flags >= 0 && d.storage_flags <= 3, "wgrad: storage_flags");
+  const bool dy_bf16 = (d.storage_flags & 1) != 0, x_bf16 = (d.storage_flags & 2) != 0;
+  HRV_REQUIRE(!(x_bf16 || dy_bf16) || d.mma_bf16, "wgrad: bf16-stored operands exist for the bf16 matrix-core kernel only");
+  HRV_REQUIRE(!dy_bf16 || x_bf16, "wgrad: storage_flags 1 (bf16 dY with fp32 X) is not built");
+  if (!d.mma_bf16) return HRV_WGRAD_F32;
+  if (x_bf16 && dy_bf16 && d.x_up_shift == 0) {     // the LDS-DMA kernels: tr, then s2, then the generic kernel
+    if (d.stride == 1 && d.Ho == d.H && d.Wo == d.W) {
+      const int cls = wgrad_tr_class(d, pl);
+      if (cls >= 0) return HRV_WGRAD_TR + cls;
+    }
+    if (d.stride == 2 && d.KH == 4 && d.KW == 4 && d.pad == 2 && d.Ho == d.H / 2 + 1 && d.Wo == d.W / 2 + 1 && wgrad_s2_class(d, pl) != 0)
+      return HRV_WGRAD_S2;
+  }
+  return HRV_WGRAD_BF16;     // (Wo % 4 == 0 is the launch's requirement: a caller may pad dY after asking)
 }
 
-static int wgrad_impl(const float* dy, int32_t dy_cstride, int32_t dy_coff, int32_t Cout, const float* x, int32_t x_C,
-                      int32_t x_cstride, int32_t x_coff, int32_t x_up_shift, int32_t x_C_real, int32_t ci_base,
-                      int32_t CinTot, int32_t N, int32_t H, int32_t W, int32_t Ho, int32_t Wo, int32_t KH, int32_t KW,
-                      int32_t stride, int32_t pad, float* workspace, int64_t workspace_bytes, float* dw_oihw,
-                      int32_t accumulate, float* dbias, int32_t dbias_accumulate, hrv_stream_t stream,
-                      const bool mma_bf16, const bool x_bf16 = false, const bool dy_bf16 = false) {
-  HRV_REQUIRE(dy && x && workspace && dw_oihw, "wgrad: null pointer");
-  HRV_REQUIRE(Cout > 0 && x_C > 0 && x_C % 4 == 0 && x_cstride % 4 == 0 && x_coff % 4 == 0 && dy_cstride % 4 == 0 &&
-                  dy_coff % 4 == 0 && x_C_real > 0 && x_C_real <= x_C && ci_base >= 0 && ci_base + x_C_real <= CinTot,
-              "wgrad: channel layout");
-  HRV_REQUIRE(N > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && KH > 0 && KW > 0 && stride > 0 && pad >= 0, "wgrad: geometry");
-  HRV_REQUIRE((((uintptr_t)dy | (uintptr_t)x | (uintptr_t)workspace) & 15) == 0, "wgrad: 16-byte alignment");
-  HRV_REQUIRE(dy_coff + Cout <= dy_cstride + 3, "wgrad: dy slice");
+extern "C" int hrv_conv2d_wgrad_route(const hrv_conv2d_wgrad_t* d) {
+  HRV_REQUIRE(d, "wgrad: null descriptor");
+  WgradLdsPlan pl;
+  return wgrad_route(*d, pl);
+}
+
+// The generic quad-staged kernels: conv_wgrad_bf16_kernel (mma_bf16; Wo % 4 == 0) or conv_wgrad_mfma_kernel.  *S_out: slabs written
+static int wgrad_generic(const hrv_conv2d_wgrad_t& d, const bool mma_bf16, hipStream_t st, int* S_out) {
+  const bool dy_bf16 = (d.storage_flags & 1) != 0, x_bf16 = (d.storage_flags & 2) != 0;
+  const int Cout = d.Cout, x_C = d.x_C, CinTot = d.CinTot;
+  float* const workspace = d.workspace;
+  float* const dbias = d.dbias;
   WgradParams p;
-  p.dy = dy; p.dy_cs = dy_cstride; p.dy_co = dy_coff; p.Cout = Cout;
-  p.x = x; p.x_C = x_C; p.x_cs = x_cstride; p.x_co = x_coff; p.x_up = x_up_shift;
-  p.N = N; p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo; p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad;
-  p.P = N * Ho * Wo; p.ci_base = ci_base; p.ci_real = x_C_real; p.CinTot = CinTot;
+  p.dy = (const float*)d.dy; p.dy_cs = d.dy_cstride; p.dy_co = d.dy_coff; p.Cout = Cout;
+  p.x = (const float*)d.x; p.x_C = x_C; p.x_cs = d.x_cstride; p.x_co = d.x_coff; p.x_up = d.x_up_shift;
+  p.N = d.N; p.H = d.H; p.W = d.W; p.Ho = d.Ho; p.Wo = d.Wo; p.KH = d.KH; p.KW = d.KW; p.stride = d.stride; p.pad = d.pad;
+  p.P = d.N * d.Ho * d.Wo; p.ci_base = d.ci_base; p.ci_real = d.x_C_real; p.CinTot = CinTot;
   p.x_bf16 = x_bf16 ? 1 : 0;
-  HRV_REQUIRE(!(x_bf16 || dy_bf16) || mma_bf16, "wgrad: bf16-stored operands exist for the bf16 matrix-core kernel only");
-  HRV_REQUIRE(!dy_bf16 || x_bf16, "wgrad: storage_flags 1 (bf16 dY with fp32 X) is not built");
-  // The conditions in front of the two tries below are repeated by train_ops.conv_wgrad, which asks hrv_conv2d_wgrad_{tr,s2}_supported
-  // under the same conditions to know which kernel will run (it pads a bf16 dY to a multiple of 4 columns for the generic kernel
-  // otherwise, and labels its launch record): edit both places together.
-  if (mma_bf16 && x_bf16 && dy_bf16 && stride == 1 && Ho == H && Wo == W && x_up_shift == 0) {
-    int S2 = 0;
-    const int r = wgrad_tr_try(dy, dy_cstride, dy_coff, Cout, x, x_C, x_cstride, x_coff, x_C_real, ci_base, CinTot, N, H, W,
-                               KH, KW, pad, workspace, workspace_bytes, dbias, dbias_accumulate, (hipStream_t)stream, &S2);
-    if (r < 0) return r;
-    if (r == 1) {      // (the kernel left its bias partials right behind the S2 weight slabs, as the kernels below do)
-      const size_t total = (size_t)Cout * x_C_real * KH * KW;
-      const int nb = grid_for(total);
-      hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(nb + (dbias ? (Cout + 15) / 16 : 0)), dim3(256), 0, (hipStream_t)stream, workspace,
-                         S2, KH * KW, Cout, CinTot, ci_base, x_C_real, dw_oihw, accumulate, nb,
-                         workspace + (size_t)S2 * KH * KW * Cout * CinTot, dbias, dbias_accumulate);
-      return check_launch("wgrad_reduce_kernel");
-    }
-  }
-  if (mma_bf16 && x_bf16 && dy_bf16 && stride == 2 && KH == 4 && KW == 4 && pad == 2 && x_up_shift == 0) {
-    int S2 = 0;
-    const int r = wgrad_s2_try(dy, dy_cstride, dy_coff, Cout, x, x_C, x_cstride, x_coff, x_C_real, ci_base, CinTot, N, H, W, Ho, Wo, workspace,
-                               workspace_bytes, dbias, (hipStream_t)stream, &S2);
-    if (r < 0) return r;
-    if (r == 1) {
-      const size_t total = (size_t)Cout * x_C_real * KH * KW;
-      const int nb = grid_for(total);
-      hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(nb + (dbias ? (Cout + 15) / 16 : 0)), dim3(256), 0, (hipStream_t)stream, workspace,
-                         S2, KH * KW, Cout, CinTot, ci_base, x_C_real, dw_oihw, accumulate, nb,
-                         workspace + (size_t)S2 * KH * KW * Cout * CinTot, dbias, dbias_accumulate);
-      return check_launch("wgrad_reduce_kernel");
-    }
-  }
   const int wt = pick_wtile(Cout, x_C);
   const int bm = wt_bm(wt), bn = wt_bn(wt);
-  p.taps = KH * KW;
+  p.taps = d.KH * d.KW;
   // column tiles over (tap, ci) (+ the "ones" column group of the fused bias gradient)
   p.co_tiles = (Cout + bm - 1) / bm; p.ci_tiles = (p.taps * x_C + (dbias ? 4 : 0) + bn - 1) / bn;
   const int tiles = p.co_tiles * p.ci_tiles;
-  HRV_REQUIRE(!mma_bf16 || Wo % 4 == 0, "wgrad (bf16 matrix cores): Wo must be a multiple of 4 (got %d)", Wo);
+  HRV_REQUIRE(!mma_bf16 || d.Wo % 4 == 0, "wgrad (bf16 matrix cores): Wo must be a multiple of 4 (got %d)", d.Wo);
   const int ptiles = mma_bf16 ? (p.P + BKP - 1) / BKP : (p.P + BK - 1) / BK;
   int S = (1024 + tiles - 1) / tiles;
   if (S > ptiles / 4) S = ptiles / 4;
   if (S > 256) S = 256;
   if (S < 1) S = 1;
   const int64_t need = ((int64_t)S * p.taps * Cout * CinTot + (dbias ? (int64_t)S * Cout : 0)) * (int64_t)sizeof(float);
-  HRV_REQUIRE(workspace_bytes >= need, "wgrad: workspace too small (%lld < %lld)", (long long)workspace_bytes, (long long)need);
+  HRV_REQUIRE(d.workspace_bytes >= need, "wgrad: workspace too small (%lld < %lld)", (long long)d.workspace_bytes, (long long)need);
   p.S = S; p.ws = workspace;
   p.bias_ws = dbias ? workspace + (size_t)S * p.taps * Cout * CinTot : nullptr;
-  hipStream_t st = (hipStream_t)stream;
   const int nblk = tiles * S;
 #define WG_CASE(I, A, B, Cc, D)                                                                                   \
   case I:                                                                                                         \
@@ -1063,56 +1039,36 @@ static int wgrad_impl(const float* dy, int32_t dy_cstride, int32_t dy_coff, int3
       return HRV_ERR_ARG;
   }
 #undef WG_CASE
-  int rc = check_launch("conv_wgrad_mfma_kernel");
+  *S_out = S;
+  return check_launch("conv_wgrad_mfma_kernel");
+}
+
+extern "C" int hrv_conv2d_wgrad(const hrv_conv2d_wgrad_t* dp, hrv_stream_t stream) {
+  HRV_REQUIRE(dp, "wgrad: null descriptor");
+  const hrv_conv2d_wgrad_t& d = *dp;
+  HRV_REQUIRE(d.dy && d.x && d.workspace && d.dw_oihw, "wgrad: null pointer");
+  HRV_REQUIRE(d.Cout > 0 && d.x_C > 0 && d.x_C % 4 == 0 && d.x_cstride % 4 == 0 && d.x_coff % 4 == 0 && d.dy_cstride % 4 == 0 &&
+                  d.dy_coff % 4 == 0 && d.x_C_real > 0 && d.x_C_real <= d.x_C && d.ci_base >= 0 && d.ci_base + d.x_C_real <= d.CinTot,
+              "wgrad: channel layout");
+  HRV_REQUIRE(d.N > 0 && d.H > 0 && d.W > 0 && d.Ho > 0 && d.Wo > 0 && d.KH > 0 && d.KW > 0 && d.stride > 0 && d.pad >= 0, "wgrad: geometry");
+  HRV_REQUIRE((((uintptr_t)d.dy | (uintptr_t)d.x | (uintptr_t)d.workspace) & 15) == 0, "wgrad: 16-byte alignment");
+  HRV_REQUIRE(d.dy_coff + d.Cout <= d.dy_cstride + 3, "wgrad: dy slice");
+  WgradLdsPlan pl;
+  const int route = wgrad_route(d, pl);
+  if (route < 0) return route;
+  hipStream_t st = (hipStream_t)stream;
+  int S = 0, rc;
+  if (route >= HRV_WGRAD_TR) { rc = wgrad_tr_try(d, pl, st); S = pl.S; }
+  else if (route == HRV_WGRAD_S2) { rc = wgrad_s2_try(d, pl, st); S = pl.S; }
+  else rc = wgrad_generic(d, route == HRV_WGRAD_BF16, st, &S);
   if (rc) return rc;
-  const size_t total = (size_t)Cout * x_C_real * p.taps;
-  const int nb = grid_for(total);
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(nb + (dbias ? (Cout + 15) / 16 : 0)), dim3(256), 0, st, workspace, S, p.taps, Cout,
-                     CinTot, ci_base, x_C_real, dw_oihw, accumulate, nb, p.bias_ws, dbias, dbias_accumulate);
+  // every kernel left S slabs of [taps][Cout][CinTot] partials in the workspace and its bias partials ([S][Cout]) right behind them
+  const int taps = d.KH * d.KW;
+  const int nb = grid_for((size_t)d.Cout * d.x_C_real * taps);
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(nb + (d.dbias ? (d.Cout + 15) / 16 : 0)), dim3(256), 0, st, d.workspace, S, taps, d.Cout,
+                     d.CinTot, d.ci_base, d.x_C_real, d.dw_oihw, d.accumulate, nb, d.workspace + (size_t)S * taps * d.Cout * d.CinTot,
+                     d.dbias, d.dbias_accumulate);
   return check_launch("wgrad_reduce_kernel");
-}
-
-extern "C" int hrv_conv2d_wgrad_nhwc_f32(const float* dy, int32_t dy_cstride, int32_t dy_coff, int32_t Cout,
-                                         const float* x, int32_t x_C, int32_t x_cstride, int32_t x_coff,
-                                         int32_t x_up_shift, int32_t x_C_real, int32_t ci_base, int32_t CinTot,
-                                         int32_t N, int32_t H, int32_t W, int32_t Ho, int32_t Wo, int32_t KH, int32_t KW,
-                                         int32_t stride, int32_t pad, float* workspace, int64_t workspace_bytes,
-                                         float* dw_oihw, int32_t accumulate, float* dbias, int32_t dbias_accumulate,
-                                         hrv_stream_t stream) {
-  return wgrad_impl(dy, dy_cstride, dy_coff, Cout, x, x_C, x_cstride, x_coff, x_up_shift, x_C_real, ci_base, CinTot, N, H,
-                    W, Ho, Wo, KH, KW, stride, pad, workspace, workspace_bytes, dw_oihw, accumulate, dbias,
-                    dbias_accumulate, stream, false);
-}
-
-// Same contract on the bf16 matrix cores (operands rounded to bf16 while staged, fp32 accumulate): the weight
-// gradient of mixed-precision training.  Requires Wo % 4 == 0.
-extern "C" int hrv_conv2d_wgrad_bf16mma_nhwc_f32(const float* dy, int32_t dy_cstride, int32_t dy_coff, int32_t Cout,
-                                                 const float* x, int32_t x_C, int32_t x_cstride, int32_t x_coff,
-                                                 int32_t x_up_shift, int32_t x_C_real, int32_t ci_base, int32_t CinTot,
-                                                 int32_t N, int32_t H, int32_t W, int32_t Ho, int32_t Wo, int32_t KH,
-                                                 int32_t KW, int32_t stride, int32_t pad, float* workspace,
-                                                 int64_t workspace_bytes, float* dw_oihw, int32_t accumulate,
-                                                 float* dbias, int32_t dbias_accumulate, hrv_stream_t stream) {
-  return wgrad_impl(dy, dy_cstride, dy_coff, Cout, x, x_C, x_cstride, x_coff, x_up_shift, x_C_real, ci_base, CinTot, N, H,
-                    W, Ho, Wo, KH, KW, stride, pad, workspace, workspace_bytes, dw_oihw, accumulate, dbias,
-                    dbias_accumulate, stream, true);
-}
-
-// Same again with bf16-STORED operands (storage_flags bit0: dY, bit1: X; element counts): activations and
-// gradients that only matrix cores read (ReLU(conv_shared(seg)), the expanded label map, [dgamma|dbeta]) are kept
-// in bf16 by the mixed-precision training plan -- the MMA operand is the same bf16 value either way.
-extern "C" int hrv_conv2d_wgrad_bf16mma_st_nhwc_f32(const void* dy, int32_t dy_cstride, int32_t dy_coff, int32_t Cout,
-                                                    const void* x, int32_t x_C, int32_t x_cstride, int32_t x_coff,
-                                                    int32_t x_up_shift, int32_t x_C_real, int32_t ci_base,
-                                                    int32_t CinTot, int32_t N, int32_t H, int32_t W, int32_t Ho,
-                                                    int32_t Wo, int32_t KH, int32_t KW, int32_t stride, int32_t pad,
-                                                    float* workspace, int64_t workspace_bytes, float* dw_oihw,
-                                                    int32_t accumulate, float* dbias, int32_t dbias_accumulate,
-                                                    int32_t storage_flags, hrv_stream_t stream) {
-  HRV_REQUIRE(storage_flags >= 0 && storage_flags <= 3, "wgrad: storage_flags");
-  return wgrad_impl((const float*)dy, dy_cstride, dy_coff, Cout, (const float*)x, x_C, x_cstride, x_coff, x_up_shift,
-                    x_C_real, ci_base, CinTot, N, H, W, Ho, Wo, KH, KW, stride, pad, workspace, workspace_bytes, dw_oihw,
-                    accumulate, dbias, dbias_accumulate, stream, true, (storage_flags & 2) != 0, (storage_flags & 1) != 0);
 }
 
 extern "C" int hrv_colsum_nhwc_f32(const float* x, int64_t P, int32_t C, int32_t cstride, int32_t coff, float* workspace,
@@ -1131,14 +1087,4 @@ extern "C" int hrv_colsum_nhwc_f32(const float* x, int64_t P, int32_t C, int32_t
   if (rc) return rc;
   hipLaunchKernelGGL(colsum_final_kernel, dim3((C + 255) / 256), dim3(256), 0, st, workspace, nb, C, Cpad, out, accumulate);
   return check_launch("colsum_final_kernel");
-}
-
-extern "C" int hrv_conv2d_wgrad_s2_supported(int32_t Cout, int32_t x_C, int32_t x_cstride, int32_t x_coff, int32_t dy_cstride, int32_t dy_coff,
-                                             int32_t N, int32_t H, int32_t W) {
-  return hrv::wgrad_s2_serves(Cout, x_C, x_cstride, x_coff, dy_cstride, dy_coff, N, H, W);
-}
-
-extern "C" int hrv_conv2d_wgrad_tr_supported(int32_t Cout, int32_t x_C, int32_t x_cstride, int32_t x_coff, int32_t dy_cstride, int32_t dy_coff,
-                                             int32_t N, int32_t H, int32_t W, int32_t KH, int32_t KW, int32_t pad) {
-  return hrv::wgrad_tr_serves(dy_cstride, dy_coff, Cout, x_C, x_cstride, x_coff, N, H, W, KH, KW, pad);
 }

@@ -221,4 +221,19 @@ inline int wgrad_workspace(const char* who, int S, int taps, int Cout, int CinTo
   return HRV_OK;
 }
 
+// Host: the shape class of a weight gradient on one of the two kernels and the block geometry that follows from it.  The route
+// (conv_bwd.hip, wgrad_route) has a class function fill it, hrv_conv2d_wgrad hands it to the same kernel's launch.
+struct WgradLdsPlan {
+  int cls;                                  // wgrad_tr: 0..8; wgrad_s2: 1 / 2
+  int tm;                                   // 32-cout tiles per wave (tr) / per block (s2)
+  int co_tiles, col_tiles, row_mode;        // (col_tiles, row_mode: tr only)
+  int gpt, tiles_per_row, n_tiles, S;
+};
+// wgrad_tr.hip, stride-1 'same' layers: the class (0..8) or -1 / launches what the class says (partials of pl.S slabs in d.workspace)
+int wgrad_tr_class(const hrv_conv2d_wgrad_t& d, WgradLdsPlan& pl);
+int wgrad_tr_try(const hrv_conv2d_wgrad_t& d, const WgradLdsPlan& pl, hipStream_t st);
+// wgrad_s2.hip, PatchGAN's 4x4 stride-2 pad-2 layers (d.Ho == d.H / 2 + 1, d.Wo == d.W / 2 + 1): the class (1 / 2) or 0 / the launch
+int wgrad_s2_class(const hrv_conv2d_wgrad_t& d, WgradLdsPlan& pl);
+int wgrad_s2_try(const hrv_conv2d_wgrad_t& d, const WgradLdsPlan& pl, hipStream_t st);
+
 }  // namespace hrv

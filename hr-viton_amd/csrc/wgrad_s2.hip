@@ -139,66 +139,50 @@ __global__ __launch_bounds__(256) void conv_wgrad_s2_kernel(const WgradS2Params 
   WGRAD_STORE(TM, TN, p, s, co0, 16, l31, lh, bias_i, acc_b, acc, b_chunk, i, kh * 4 + b_kw[j], true)
 }
 
-// The slab count of a shape class (tm: 32-cout tiles per block) and whether every slab's extent fits the kernel's 31-bit scalar offsets
-static bool wgrad_s2_slabs(int tm, int Cout, int x_cs, int dy_cs, int N, int H, int W, int& S) {
-  const int Ho = H / 2 + 1, Wo = W / 2 + 1;
-  const int tiles_per_row = (Wo + 63) / 64;
-  const int n_tiles = N * Ho * tiles_per_row;
-  // X is addressed from two rows before the input row of the slab's first dY row, two input rows per dY row
-  return wgrad_slabs(Cout / (32 * tm) * 4, n_tiles, tiles_per_row, 4, (long long)Wo * dy_cs * 2, 8, 2LL * W * x_cs * 2, S);
-}
-
-// 1 / 2: the shape class the kernel serves (EVERY condition wgrad_s2_try applies before it launches: hrv_conv2d_wgrad_s2_supported
-// answers from it, and its caller pads a bf16 dY for the fallback kernel when the answer is no), 0: none.  S: the class's slab count
-static int wgrad_s2_class(int Cout, int x_C, int x_cs, int x_co, int dy_cs, int dy_co, int N, int H, int W, int& S) {
+// 1 / 2: the shape class the kernel serves -- EVERY condition on the shape behind the route's front conditions (wgrad_route,
+// conv_bwd.hip: bf16 storage, no resampling, 4x4 stride 2 pad 2, Ho == H / 2 + 1, Wo == W / 2 + 1), HRV_WGRAD_S2 and the
+// slab-extent limit included -- or 0: none.  Fills `pl`.
+int wgrad_s2_class(const hrv_conv2d_wgrad_t& d, WgradLdsPlan& pl) {
+  const int Cout = d.Cout, x_C = d.x_C, N = d.N, H = d.H, W = d.W, Ho = d.Ho, Wo = d.Wo;
   const char* env = hrv::env("HRV_WGRAD_S2");
   if (env && env[0] == '0') return 0;
   if (Cout < 1 || x_C < 1 || N < 1 || H < 1 || W < 1) return 0;
-  if ((dy_cs | dy_co | x_cs | x_co | x_C) & 7) return 0;                         // 16-byte DMA granules
-  const int Ho = H / 2 + 1, Wo = W / 2 + 1;
+  if ((d.dy_cstride | d.dy_coff | d.x_cstride | d.x_coff | x_C) & 7) return 0;   // 16-byte DMA granules
   if ((long long)N * Ho * Wo < 8192 || Wo < 32) return 0;
   const int gpt = (x_C + 31) / 32;
   int c_ = 0;
-  S = 0;
   if (gpt == 2 && Cout % 128 == 0) c_ = 1;              // 64 -> 128 (model1): 128 couts x (4 kw x 2 chunks)
   else if (gpt == 4 && Cout % 64 == 0) c_ = 2;          // 128 -> 256 (model2): 64 couts x (4 kw x 4 chunks)
-  if (c_ == 0 || !wgrad_s2_slabs(c_ == 1 ? 4 : 2, Cout, x_cs, dy_cs, N, H, W, S)) return 0;
+  if (c_ == 0) return 0;
+  pl.cls = c_; pl.tm = c_ == 1 ? 4 : 2;
+  pl.gpt = gpt;
+  pl.co_tiles = Cout / (32 * pl.tm); pl.col_tiles = 4; pl.row_mode = 0;       // (a block: one kernel row kh)
+  pl.tiles_per_row = (Wo + 63) / 64;
+  pl.n_tiles = N * Ho * pl.tiles_per_row;
+  // X is addressed from two rows before the input row of the slab's first dY row, two input rows per dY row
+  if (!wgrad_slabs(pl.co_tiles * 4, pl.n_tiles, pl.tiles_per_row, 4, (long long)Wo * d.dy_cstride * 2, 8, 2LL * W * d.x_cstride * 2, pl.S))
+    return 0;
   return c_;
 }
-int wgrad_s2_serves(int Cout, int x_C, int x_cs, int x_co, int dy_cs, int dy_co, int N, int H, int W) {
-  int S = 0;
-  return wgrad_s2_class(Cout, x_C, x_cs, x_co, dy_cs, dy_co, N, H, W, S) != 0 ? 1 : 0;
-}
 
-// Host side.  Returns 1 when the kernel was launched (partials in `workspace`, *S_out slabs), 0 when the shape is not one it
-// serves (the caller falls back to conv_wgrad_bf16_kernel), < 0 on error.
-int wgrad_s2_try(const void* dy, int dy_cs, int dy_co, int Cout, const void* x, int x_C, int x_cs, int x_co, int x_C_real, int ci_base,
-                 int CinTot, int N, int H, int W, int Ho, int Wo, float* workspace, long long workspace_bytes, float* dbias, hipStream_t st,
-                 int* S_out) {
-  if (Ho != H / 2 + 1 || Wo != W / 2 + 1) return 0;
-  int S = 0;
-  const int c_ = wgrad_s2_class(Cout, x_C, x_cs, x_co, dy_cs, dy_co, N, H, W, S);
-  if (c_ == 0) return 0;
-  const int cls = c_ - 1, tm = c_ == 1 ? 4 : 2;
-  const int gpt = (x_C + 31) / 32;
+// Host side: launches the instance of class `pl` (from wgrad_s2_class over this `d`); the partials of pl.S slabs are left in
+// d.workspace, the bias column sums right behind them, for the caller's wgrad_reduce_kernel launch.  HRV_OK or < 0.
+int wgrad_s2_try(const hrv_conv2d_wgrad_t& d, const WgradLdsPlan& pl, hipStream_t st) {
   WgradS2Params p;
-  p.dy = dy; p.dy_cs = dy_cs; p.dy_co = dy_co; p.Cout = Cout;
-  p.x = x; p.x_cs = x_cs; p.x_co = x_co; p.x_C = x_C;
-  p.N = N; p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo;
-  p.CinTot = CinTot; p.ci_base = ci_base; p.ci_real = x_C_real;
-  p.gpt = gpt;
-  p.co_tiles = Cout / (32 * tm);
-  p.tiles_per_row = (Wo + 63) / 64;
-  p.n_tiles = N * Ho * p.tiles_per_row;
-  p.S = S; p.ws = workspace;
-  if (int rc = wgrad_workspace("wgrad_s2", S, 16, Cout, CinTot, workspace, workspace_bytes, dbias != nullptr, p.bias_ws)) return rc;
-  const int nblk = p.co_tiles * 4 * S;
-  if (cls == 0) hipLaunchKernelGGL((conv_wgrad_s2_kernel<4, 2, 2>), dim3(nblk), dim3(256), 0, st, p);
+  p.dy = d.dy; p.dy_cs = d.dy_cstride; p.dy_co = d.dy_coff; p.Cout = d.Cout;
+  p.x = d.x; p.x_cs = d.x_cstride; p.x_co = d.x_coff; p.x_C = d.x_C;
+  p.N = d.N; p.H = d.H; p.W = d.W; p.Ho = d.Ho; p.Wo = d.Wo;
+  p.CinTot = d.CinTot; p.ci_base = d.ci_base; p.ci_real = d.x_C_real;
+  p.gpt = pl.gpt;
+  p.co_tiles = pl.co_tiles;
+  p.tiles_per_row = pl.tiles_per_row;
+  p.n_tiles = pl.n_tiles;
+  p.S = pl.S; p.ws = d.workspace;
+  if (int rc = wgrad_workspace("wgrad_s2", pl.S, 16, d.Cout, d.CinTot, d.workspace, d.workspace_bytes, d.dbias != nullptr, p.bias_ws)) return rc;
+  const int nblk = p.co_tiles * 4 * pl.S;
+  if (pl.cls == 1) hipLaunchKernelGGL((conv_wgrad_s2_kernel<4, 2, 2>), dim3(nblk), dim3(256), 0, st, p);
   else hipLaunchKernelGGL((conv_wgrad_s2_kernel<2, 4, 4>), dim3(nblk), dim3(256), 0, st, p);
-  int rc = check_launch("conv_wgrad_s2_kernel");
-  if (rc) return rc;
-  *S_out = S;
-  return 1;
+  return check_launch("conv_wgrad_s2_kernel");
 }
 
 }  // namespace hrv

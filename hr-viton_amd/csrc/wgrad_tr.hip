@@ -170,17 +170,16 @@ __global__ __launch_bounds__(256) void conv_wgrad_tr_kernel(const WgradTrParams 
   WGRAD_STORE(TM, TN, p, s, co0, taps, l31, lh, bias_i, acc_b, acc, b_chunk, wm * TM + i, b_tap[j], b_tap[j] < taps)
 }
 
-// The shape class (0..8) that serves this weight gradient, or -1: EVERY condition wgrad_tr_try applies before it launches, the
-// environment switches and the slab-extent limit included.  Fills the geometry fields of `p`, the cout tiles per wave `tm` and the
-// slab count `S`.  hrv_conv2d_wgrad_tr_supported answers from it as well, so a caller that has to prepare its operands differently
-// for the fallback kernel (train_ops.conv_wgrad: a bf16 dY padded to a multiple of 4 columns) asks the same code that decides.
-static int wgrad_tr_class(int dy_cs, int dy_co, int Cout, int x_C, int x_cs, int x_co, int N, int H, int W, int KH, int KW, int pad,
-                          WgradTrParams& p, int& tm, int& S) {
+// The shape class (0..8) that serves this weight gradient, or -1: EVERY condition on the shape behind the route's front conditions
+// (wgrad_route, conv_bwd.hip: bf16 storage, no resampling, stride 1, Ho == H, Wo == W), the environment switches and the slab-extent
+// limit included.  Fills `pl`.
+int wgrad_tr_class(const hrv_conv2d_wgrad_t& d, WgradLdsPlan& pl) {
+  const int Cout = d.Cout, x_C = d.x_C, N = d.N, H = d.H, W = d.W, KH = d.KH, KW = d.KW;
   const char* env = hrv::env("HRV_WGRAD_TR");
   if (env && env[0] == '0') return -1;
-  if (KW < 1 || KW > 3 || KH != KW || pad != KH / 2) return -1;
+  if (KW < 1 || KW > 3 || KH != KW || d.pad != KH / 2) return -1;
   if (Cout < 1 || x_C < 1 || N < 1 || H < 1 || W < 1) return -1;
-  if ((dy_cs | dy_co | x_cs | x_co | x_C) & 7) return -1;                        // 16-byte DMA granules (Cout itself may be
+  if ((d.dy_cstride | d.dy_coff | d.x_cstride | d.x_coff | x_C) & 7) return -1;  // 16-byte DMA granules (Cout itself may be
                                                                                   // anything: rows >= Cout are never written)
   const long long P = (long long)N * H * W;
   // low-resolution levels: weight-bound, old kernel.  HRV_WGRAD_TR_MIN_PIX: the smallest N*H*W this kernel takes -- 8192 since round 5
@@ -191,76 +190,72 @@ static int wgrad_tr_class(int dy_cs, int dy_co, int Cout, int x_C, int x_cs, int
   if (P < (pmin > 0 ? pmin : 8192) || W < 32) return -1;
   const int gpt = (x_C + 31) / 32;
   const int taps = KH * KW;
-  p.dy_cs = dy_cs; p.dy_co = dy_co; p.Cout = Cout;
-  p.x_cs = x_cs; p.x_co = x_co; p.x_C = x_C;
-  p.N = N; p.H = H; p.W = W; p.KH = KH; p.KW = KW; p.pad = pad;
-  p.gpt = gpt;
-  p.tiles_per_row = (W + 63) / 64;
-  p.n_tiles = N * H * p.tiles_per_row;
+  pl.gpt = gpt;
+  pl.tiles_per_row = (W + 63) / 64;
+  pl.n_tiles = N * H * pl.tiles_per_row;
   // shape classes:  0 = 128-channel source, a block = the KW taps of one kernel row x all 128 channels x <= 160 couts
   //                 1..3 = thin layers (<= 32 couts, <= 96 source channels): a block = every tap x every channel
   //                 4..7 = other source widths (round 4): 4: 144 / 160 channels (5 groups), 6: 272 / 288 (9), 7: 256 (8) -- a block =
   //                        the KW taps of one kernel row x all groups x 64 couts (row mode); 5: 64 channels x 64 couts, every tap
-  int cls = -1;
-  tm = 0;
-  p.row_mode = 0;
+  int cls = -1, tm = 0;
+  pl.row_mode = 0;
   if (gpt == 4 && KW == 3) {
     cls = 0;
-    p.co_tiles = (Cout + 159) / 160;
-    tm = (((Cout + p.co_tiles - 1) / p.co_tiles) + 31) / 32;                     // 1..5
-    p.col_tiles = KH * KW * gpt / 12;                                              // WN 4 x TN 3 groups per block
+    pl.co_tiles = (Cout + 159) / 160;
+    tm = (((Cout + pl.co_tiles - 1) / pl.co_tiles) + 31) / 32;                   // 1..5
+    pl.col_tiles = KH * KW * gpt / 12;                                             // WN 4 x TN 3 groups per block
   } else if (KW == 3 && Cout % 64 == 0 && (gpt == 5 || gpt == 9 || gpt == 8)) {
     cls = gpt == 5 ? 4 : (gpt == 9 ? 6 : 7);
-    p.row_mode = 1;
-    p.co_tiles = Cout / 64; tm = 2;
-    p.col_tiles = KH;
+    pl.row_mode = 1;
+    pl.co_tiles = Cout / 64; tm = 2;
+    pl.col_tiles = KH;
   } else if (KW == 3 && Cout % 64 == 0 && gpt == 2) {
     cls = 5;
-    p.co_tiles = Cout / 64; tm = 2;
-    p.col_tiles = 1;
+    pl.co_tiles = Cout / 64; tm = 2;
+    pl.col_tiles = 1;
   } else if (KW == 2 && Cout % 64 == 0 && gpt == 2) {
     cls = 8;      // 2x2 over <= 64 channels (round 6: PatchGAN's model0 over its space-to-depth image, conv_s2.hip mode 2)
-    p.co_tiles = Cout / 64; tm = 2;
-    p.col_tiles = 1;
+    pl.co_tiles = Cout / 64; tm = 2;
+    pl.col_tiles = 1;
   } else if (Cout <= 32 && taps * gpt <= 28 && gpt <= 3) {
     cls = gpt == 3 ? (taps == 1 ? 3 : 1) : (gpt == 1 && taps == 9 ? 2 : -1);
-    p.co_tiles = 1; p.col_tiles = 1; tm = 1;
+    pl.co_tiles = 1; pl.col_tiles = 1; tm = 1;
   }
   if (cls < 0 || tm < 1 || tm > 5) return -1;
   // both operands are addressed from the slab's first row: either's extent is the slab's rows + 4 + KH
-  if (!wgrad_slabs(p.co_tiles * p.col_tiles, p.n_tiles, p.tiles_per_row, 4 + KH, (long long)W * dy_cs * 2, 4 + KH, (long long)W * x_cs * 2, S))
+  if (!wgrad_slabs(pl.co_tiles * pl.col_tiles, pl.n_tiles, pl.tiles_per_row, 4 + KH, (long long)W * d.dy_cstride * 2, 4 + KH,
+                   (long long)W * d.x_cstride * 2, pl.S))
     return -1;
+  pl.cls = cls; pl.tm = tm;
   return cls;
 }
 
-int wgrad_tr_serves(int dy_cs, int dy_co, int Cout, int x_C, int x_cs, int x_co, int N, int H, int W, int KH, int KW, int pad) {
+// Host side: launches the instance of class `pl` (from wgrad_tr_class over this `d`); the partials of pl.S slabs are left in
+// d.workspace, the bias column sums ([S][Cout]) right behind them, for the caller's wgrad_reduce_kernel launch.  HRV_OK or < 0.
+int wgrad_tr_try(const hrv_conv2d_wgrad_t& d, const WgradLdsPlan& pl, hipStream_t st) {
   WgradTrParams p;
-  int tm = 0, S = 0;
-  return wgrad_tr_class(dy_cs, dy_co, Cout, x_C, x_cs, x_co, N, H, W, KH, KW, pad, p, tm, S) + 1;
-}
-
-// Host side.  Returns 1 when the kernel was launched (partials in `workspace`, *S_out slabs), 0 when the shape is
-// not one it serves (the caller falls back to conv_wgrad_bf16_kernel), < 0 on error.
-int wgrad_tr_try(const void* dy, int dy_cs, int dy_co, int Cout, const void* x, int x_C, int x_cs, int x_co, int x_C_real,
-                 int ci_base, int CinTot, int N, int H, int W, int KH, int KW, int pad, float* workspace,
-                 long long workspace_bytes, float* dbias, int dbias_accumulate, hipStream_t st, int* S_out) {
-  WgradTrParams p;
-  int tm = 0, S = 0;
-  const int cls = wgrad_tr_class(dy_cs, dy_co, Cout, x_C, x_cs, x_co, N, H, W, KH, KW, pad, p, tm, S);
-  if (cls < 0) return 0;
-  p.dy = dy; p.x = x;
-  p.CinTot = CinTot; p.ci_base = ci_base; p.ci_real = x_C_real;
-  p.S = S; p.ws = workspace;
-  if (int rc = wgrad_workspace("wgrad_tr", S, KH * KW, Cout, CinTot, workspace, workspace_bytes, dbias != nullptr, p.bias_ws)) return rc;
-  const int nblk = p.co_tiles * p.col_tiles * S;
+  p.dy = d.dy; p.dy_cs = d.dy_cstride; p.dy_co = d.dy_coff; p.Cout = d.Cout;
+  p.x = d.x; p.x_cs = d.x_cstride; p.x_co = d.x_coff; p.x_C = d.x_C;
+  p.N = d.N; p.H = d.H; p.W = d.W; p.KH = d.KH; p.KW = d.KW; p.pad = d.pad;
+  p.CinTot = d.CinTot; p.ci_base = d.ci_base; p.ci_real = d.x_C_real;
+  p.co_tiles = pl.co_tiles; p.col_tiles = pl.col_tiles; p.S = pl.S;
+  p.gpt = pl.gpt; p.row_mode = pl.row_mode;
+  p.tiles_per_row = pl.tiles_per_row; p.n_tiles = pl.n_tiles;
+  p.ws = d.workspace;
+  if (int rc = wgrad_workspace("wgrad_tr", pl.S, d.KH * d.KW, d.Cout, d.CinTot, d.workspace, d.workspace_bytes, d.dbias != nullptr, p.bias_ws))
+    return rc;
+  const int nblk = p.co_tiles * p.col_tiles * pl.S;
+  const int cls = pl.cls;
   if (cls == 0) {
-    switch (tm) {
+    switch (pl.tm) {
       case 1: hipLaunchKernelGGL((conv_wgrad_tr_kernel<1, 3, 1, 4, 4, 1>), dim3(nblk), dim3(256), 0, st, p); break;
       case 2: hipLaunchKernelGGL((conv_wgrad_tr_kernel<2, 3, 1, 4, 4, 1>), dim3(nblk), dim3(256), 0, st, p); break;
       case 3: hipLaunchKernelGGL((conv_wgrad_tr_kernel<3, 3, 1, 4, 4, 1>), dim3(nblk), dim3(256), 0, st, p); break;
       case 4: hipLaunchKernelGGL((conv_wgrad_tr_kernel<4, 3, 1, 4, 4, 1>), dim3(nblk), dim3(256), 0, st, p); break;
       case 5: hipLaunchKernelGGL((conv_wgrad_tr_kernel<5, 3, 1, 4, 4, 1>), dim3(nblk), dim3(256), 0, st, p); break;
-      default: return 0;
+      default:
+        set_error("wgrad_tr: no instance for %d cout tiles per wave", pl.tm);
+        return HRV_ERR_ARG;
     }
   } else if (cls == 4) {      // 3x3 over 144 / 160 channels: 15 groups per kernel row -> 4 waves x 4
     hipLaunchKernelGGL((conv_wgrad_tr_kernel<2, 4, 1, 4, 5, 1>), dim3(nblk), dim3(256), 0, st, p);
@@ -279,11 +274,7 @@ int wgrad_tr_try(const void* dy, int dy_cs, int dy_co, int Cout, const void* x, 
   } else {                    // 1x1 over <= 96 channels: 3 groups -> 4 waves x 1
     hipLaunchKernelGGL((conv_wgrad_tr_kernel<1, 1, 1, 4, 3, 1>), dim3(nblk), dim3(256), 0, st, p);
   }
-  int rc = check_launch("conv_wgrad_tr_kernel");
-  if (rc) return rc;
-  (void)dbias_accumulate;     // the caller's reduce launch sums bias_ws ([S][Cout], right behind the S weight slabs) as well
-  *S_out = S;
-  return 1;
+  return check_launch("conv_wgrad_tr_kernel");
 }
 
 }  // namespace hrv

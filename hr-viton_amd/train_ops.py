@@ -12,7 +12,7 @@ import torch
 
 from . import _lib, ops
 from .conv_dispatch import (COUT1, MMA_BF16, P2, THIN, conv_p2_ok, plan_dgrad, plan_forward,  # noqa: F401  (MMA_BF16, conv_p2_ok: used
-                            plan_wgrad)                                                        # through this module by callers)
+                            plan_wgrad, wgrad_desc)                                            # through this module by callers)
 from .ops import ACT_LRELU, ACT_NONE, ACT_RELU, Act, _ceil4, _stream, _Timed, _workspace
 
 
@@ -605,11 +605,10 @@ def conv_dgrad(dy: Act, w, H: int, W: int, stride: int, pad: int, wscale: float 
 def conv_wgrad(dy: Act, x: Act, x_up: int, ci_base: int, cin_tot: int, KH: int, KW: int, stride: int, pad: int,
                dw: torch.Tensor, accumulate: bool = False, name: str = "wgrad", dbias: Optional[torch.Tensor] = None,
                dbias_accumulate: bool = False):
-    """dW[:, ci_base:ci_base+x.C] (+)= wgrad(dY, x) -- hrv_conv2d_wgrad_nhwc_f32.  ``dw``: OIHW fp32 device.
+    """dW[:, ci_base:ci_base+x.C] (+)= wgrad(dY, x) -- hrv_conv2d_wgrad.  ``dw``: OIHW fp32 device.
     ``dbias`` ([Cout], optional): the bias gradient, fused as a ones-column of the same reduction."""
     lib = _lib.load()
     N, Ho, Wo, Cout = dy.N, dy.H, dy.W, dy.C
-    H, W = (x.H << x_up, x.W << x_up) if x_up >= 0 else (x.H >> -x_up, x.W >> -x_up)
     assert dw.is_contiguous() and tuple(dw.shape) == (Cout, cin_tot, KH, KW), (dw.shape, Cout, cin_tot, KH, KW)
     p = plan_wgrad(dy, x, x_up, ci_base, cin_tot, KH, KW, stride, pad, dw)
     fl = 2.0 * N * Ho * Wo * Cout * x.C * KH * KW
@@ -622,22 +621,22 @@ def conv_wgrad(dy: Act, x: Act, x_up: int, ci_base: int, cin_tot: int, KH: int, 
         with _Timed("wgrad", name, fl, ops.act_bytes(x) + 4.0 * N * Ho * Wo, COUT1):
             _lib.check(lib.hrv_conv_cout1_wgrad_f32(C.byref(d), *acc, _stream()), f"hrv_conv_cout1_wgrad_f32[{name}]")
         return
-    if p.pad == "bf16":
-        dy = pad_width_bf16(dy)
-    elif p.pad == "f32":
-        with _Timed("layout", "pad_width", 0.0, 2.0 * ops.act_bytes(dy)):
-            dy = Act(torch.nn.functional.pad(dy.t, (0, 0, 0, (-Wo) % 4)), dy.C)
-    Wo = dy.W
-    need = lib.hrv_conv2d_wgrad_workspace_bytes(Cout, cin_tot, KH, KW, N * Ho * Wo)
-    ws = _workspace(dy.t.device, need)
-    args = (dy.t.data_ptr(), dy.cstride, dy.coff, Cout, x.t.data_ptr(), x.Cp, x.cstride, x.coff, x_up, x.C, ci_base,
-            cin_tot, N, H, W, Ho, Wo, KH, KW, stride, pad, ws.data_ptr(), ws.numel() * 4, *acc)
-    if p.entry == "hrv_conv2d_wgrad_bf16mma_st_nhwc_f32":       # (storage flags: bit 0 a bf16 dY, bit 1 a bf16 X)
-        args += ((1 if dy.bf16 else 0) | 2,)
+    d = p.desc
+    if p.pad:
+        if p.pad == "bf16":
+            dy = pad_width_bf16(dy)
+        else:
+            with _Timed("layout", "pad_width", 0.0, 2.0 * ops.act_bytes(dy)):
+                dy = Act(torch.nn.functional.pad(dy.t, (0, 0, 0, (-Wo) % 4)), dy.C)
+        Wo = dy.W
+        d = wgrad_desc(dy, x, x_up, ci_base, cin_tot, KH, KW, stride, pad, bool(d.mma_bf16))      # (of the padded dY)
+    ws = _workspace(dy.t.device, lib.hrv_conv2d_wgrad_workspace_bytes(Cout, cin_tot, KH, KW, N * Ho * Wo))
+    d.dy, d.x, d.workspace, d.workspace_bytes = dy.t.data_ptr(), x.t.data_ptr(), ws.data_ptr(), ws.numel() * 4
+    d.dw_oihw, d.accumulate, d.dbias, d.dbias_accumulate = acc
     nbytes = ops.act_bytes(dy) + ops.act_bytes(x) + 4.0 * Cout * x.C * KH * KW
     # (the record names the device kernel that serves the launch -- what a rocprofv3 kernel trace groups by)
     with _Timed("wgrad", name, fl, nbytes, p.kernel, p.variant):
-        _lib.check(getattr(lib, p.entry)(*args, _stream()), p.entry)
+        _lib.check(lib.hrv_conv2d_wgrad(C.byref(d), _stream()), f"hrv_conv2d_wgrad[{name}]")
 
 
 def colsum(a: Act, out: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:

@@ -226,31 +226,45 @@ int hrv_conv2d_pack_weight_record(const float* w_oihw_dev, int32_t Cout, int32_t
 int hrv_conv2d_pack_weight_multi(const void* records_dev, const int32_t* first_block_dev, int32_t n, int32_t blocks,
                                  hrv_stream_t stream);
 int64_t hrv_conv2d_wgrad_workspace_bytes(int32_t Cout, int32_t CinTot, int32_t KH, int32_t KW, int64_t P);
-int hrv_conv2d_wgrad_nhwc_f32(const float* dy, int32_t dy_cstride, int32_t dy_coff, int32_t Cout, const float* x,
-                              int32_t x_C, int32_t x_cstride, int32_t x_coff, int32_t x_up_shift, int32_t x_C_real,
-                              int32_t ci_base, int32_t CinTot, int32_t N, int32_t H, int32_t W, int32_t Ho, int32_t Wo,
-                              int32_t KH, int32_t KW, int32_t stride, int32_t pad, float* workspace,
-                              int64_t workspace_bytes, float* dw_oihw, int32_t accumulate, float* dbias,
-                              int32_t dbias_accumulate, hrv_stream_t stream);
-/* dbias (optional, [Cout]): the bias gradient sum_pixels dY[:, co], fused as one extra "ones" column of the same
- * MFMA reduction (no second pass over dY; deterministic).  Pass it with the FIRST source of a concatenation only.
- * Same contract with the operands rounded to bf16 while staged and multiplied on v_mfma_f32_32x32x16_bf16 (fp32
- * accumulate): the weight gradient of mixed-precision training.  Requires Wo % 4 == 0. */
-int hrv_conv2d_wgrad_bf16mma_nhwc_f32(const float* dy, int32_t dy_cstride, int32_t dy_coff, int32_t Cout, const float* x,
-                              int32_t x_C, int32_t x_cstride, int32_t x_coff, int32_t x_up_shift, int32_t x_C_real,
-                              int32_t ci_base, int32_t CinTot, int32_t N, int32_t H, int32_t W, int32_t Ho, int32_t Wo,
-                              int32_t KH, int32_t KW, int32_t stride, int32_t pad, float* workspace,
-                              int64_t workspace_bytes, float* dw_oihw, int32_t accumulate, float* dbias,
-                              int32_t dbias_accumulate, hrv_stream_t stream);
-/* Same again with bf16-STORED operands: storage_flags bit0 = `dy` points at bf16 elements, bit1 = `x` does
- * (counts in elements, multiples of 4).  Tensors that only matrix cores read are kept in bf16 by the
- * mixed-precision training plan (same MMA operand bits, half the bytes).  Supported: 0, 2 (x), 3 (both). */
-int hrv_conv2d_wgrad_bf16mma_st_nhwc_f32(const void* dy, int32_t dy_cstride, int32_t dy_coff, int32_t Cout,
-                              const void* x, int32_t x_C, int32_t x_cstride, int32_t x_coff, int32_t x_up_shift,
-                              int32_t x_C_real, int32_t ci_base, int32_t CinTot, int32_t N, int32_t H, int32_t W,
-                              int32_t Ho, int32_t Wo, int32_t KH, int32_t KW, int32_t stride, int32_t pad,
-                              float* workspace, int64_t workspace_bytes, float* dw_oihw, int32_t accumulate,
-                              float* dbias, int32_t dbias_accumulate, int32_t storage_flags, hrv_stream_t stream);
+/* dy / x: fp32 elements, or bf16 where storage_flags says so -- bit0: `dy` points at bf16 elements, bit1: `x` does (counts in
+ * elements, multiples of 4).  Tensors that only matrix cores read are kept in bf16 by the mixed-precision training plan (same MMA
+ * operand bits, half the bytes).  Supported: 0, 2 (x), 3 (both); bf16 storage needs mma_bf16.
+ * mma_bf16 1: the operands are rounded to bf16 while staged and multiplied on v_mfma_f32_32x32x16_bf16 (fp32 accumulate) -- the
+ * weight gradient of mixed-precision training; 0: fp32 MFMA.
+ * dbias (optional, [Cout]): the bias gradient sum_pixels dY[:, co], fused as one extra "ones" column of the same
+ * MFMA reduction (no second pass over dY; deterministic).  Pass it with the FIRST source of a concatenation only. */
+typedef struct hrv_conv2d_wgrad {
+  const void* dy;       /* NHWC [N][Ho][Wo], Cout channels at dy_coff of dy_cstride                       */
+  int32_t dy_cstride, dy_coff, Cout;
+  int32_t x_C;          /* channels taken from x (padded: a multiple of 4)                               */
+  const void* x;        /* NHWC source, read through x_up_shift as hrv_src_t.up_shift                    */
+  int32_t x_cstride, x_coff, x_up_shift;
+  int32_t x_C_real;     /* channels of x that exist in the weight (<= x_C)                               */
+  int32_t ci_base, CinTot; /* dW[:, ci_base : ci_base + x_C_real] of a weight with CinTot input channels */
+  int32_t N, H, W;      /* conv input extent (after any folded resampling of x)                          */
+  int32_t Ho, Wo;       /* extent of dy                                                                  */
+  int32_t KH, KW, stride, pad;
+  int32_t mma_bf16, storage_flags;
+  int32_t _pad;
+  float* workspace;         /* >= hrv_conv2d_wgrad_workspace_bytes(Cout, CinTot, KH, KW, N*Ho*Wo)        */
+  int64_t workspace_bytes;
+  float* dw_oihw;       /* [Cout][CinTot][KH][KW] fp32                                                   */
+  float* dbias;         /* [Cout] or NULL                                                                */
+  int32_t accumulate, dbias_accumulate;     /* 1: += into dw_oihw / dbias                                */
+} hrv_conv2d_wgrad_t;
+/* The kernel that serves a descriptor.  The LDS-DMA kernels (wgrad_tr.hip: stride-1 'same' layers, wgrad_s2.hip: PatchGAN's 4x4
+ * stride-2 pad-2 layers; both operands bf16-stored, any output width) go first, then the generic quad-staged kernels. */
+enum hrv_wgrad_route {
+  HRV_WGRAD_F32 = 0,    /* conv_wgrad_mfma_kernel                                                         */
+  HRV_WGRAD_BF16 = 1,   /* conv_wgrad_bf16_kernel: needs Wo % 4 == 0 at launch (hrv_pad_width_nhwc_bf16)  */
+  HRV_WGRAD_S2 = 2,     /* conv_wgrad_s2_kernel                                                           */
+  HRV_WGRAD_TR = 3      /* conv_wgrad_tr_kernel: HRV_WGRAD_TR + its shape class 0..8                      */
+};
+/* HOST function, launches nothing: the hrv_wgrad_route hrv_conv2d_wgrad takes for `d`, from the very code that launches (the
+ * HRV_WGRAD_TR / HRV_WGRAD_TR_MIN_PIX / HRV_WGRAD_S2 switches, the pixel, width, granule and slab-extent limits included), or
+ * HRV_ERR_ARG for a storage form that is not built.  Reads metadata only: the pointers of `d` may be NULL. */
+int hrv_conv2d_wgrad_route(const hrv_conv2d_wgrad_t* d);
+int hrv_conv2d_wgrad(const hrv_conv2d_wgrad_t* d, hrv_stream_t stream);
 int hrv_colsum_nhwc_f32(const float* x, int64_t P, int32_t C, int32_t cstride, int32_t coff, float* workspace,
                         int64_t workspace_bytes, float* out, int32_t accumulate, hrv_stream_t stream);
 
@@ -865,7 +879,7 @@ int hrv_conv_s2_bf16(const hrv_conv_s2_t* d, hrv_stream_t stream);
  * (cf. hrv_scale_f32), and out[r][w] = w < W ? in[r][w] : 0 for a dY whose width the quad-staged weight gradient needs padded to 4. */
 /* the space-to-depth image of model0's input (cf. hrv_space_to_depth2_nhwc_f32) in bf16 over Hp x Wp cells (>= H/2 x W/2; cells and
  * sub-pixels outside the image are zeros: with a one-cell border model0
- * is a 'same' 2x2 convolution, the shape hrv_conv2d_wgrad_bf16mma_st_nhwc_f32's LDS-DMA kernel serves), optionally as [hi | lo | hi] */
+ * is a 'same' 2x2 convolution, a shape hrv_conv2d_wgrad's LDS-DMA kernel serves), optionally as [hi | lo | hi] */
 int hrv_space_to_depth2_cells_bf16(const float* in, int32_t N, int32_t H, int32_t W, int32_t C, int32_t in_cstride, int32_t in_coff,
                                    int32_t Hp, int32_t Wp, int32_t split3, uint16_t* out, hrv_stream_t stream);
 int hrv_instnorm_apply_nhwc_bf16out(const float* x, int32_t N, int32_t H, int32_t W, int32_t C, int32_t cstride, int32_t coff,
@@ -874,16 +888,6 @@ int hrv_instnorm_apply_nhwc_bf16out(const float* x, int32_t N, int32_t H, int32_
 int hrv_scale_bf16(uint16_t* x, int64_t n, float s_host, const float* s_dev, hrv_stream_t stream);
 /* out[p] = [hi(x[p]) | bf16(x[p] - hi(x[p])) | hi(x[p])] (3 C bf16 channels, dense) of an fp32 NHWC slice: see HRV_S2_SPLIT3 */
 int hrv_split3_nhwc_bf16(const float* x, int64_t npix, int32_t C, int32_t cstride, int32_t coff, uint16_t* out, hrv_stream_t stream);
-/* 1: hrv_conv2d_wgrad_bf16mma_st_nhwc_f32 serves this 4x4 stride-2 pad-2 layer (bf16-stored dY and X) with the
- * LDS-DMA kernel of wgrad_s2.hip -- any output width; 0: the quad-staged kernel, which needs Wo % 4 == 0 (hrv_pad_width_nhwc_bf16).
- * The answer is the launch path's own decision (HRV_WGRAD_S2 and the slab-extent limit included). */
-int hrv_conv2d_wgrad_s2_supported(int32_t Cout, int32_t x_C, int32_t x_cstride, int32_t x_coff, int32_t dy_cstride, int32_t dy_coff,
-                                  int32_t N, int32_t H, int32_t W);
-/* The same question for the stride-1 'same' layers of wgrad_tr.hip (bf16-stored dY and X, x_up_shift 0, Ho == H, Wo == W): 0, or
- * 1 + the shape class (0..8) that the launch path will take -- HRV_WGRAD_TR, HRV_WGRAD_TR_MIN_PIX, the width and slab-extent limits
- * included.  x_C: padded channels of the source (a multiple of 8). */
-int hrv_conv2d_wgrad_tr_supported(int32_t Cout, int32_t x_C, int32_t x_cstride, int32_t x_coff, int32_t dy_cstride, int32_t dy_coff,
-                                  int32_t N, int32_t H, int32_t W, int32_t KH, int32_t KW, int32_t pad);
 int hrv_pad_width_nhwc_bf16(const uint16_t* in, int64_t rows, int32_t W, int32_t C, int32_t Wp, uint16_t* out, hrv_stream_t stream);
 
 /* ---- evaluation metrics (evaluate.py; metrics.hip) ---- */

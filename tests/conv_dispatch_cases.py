@@ -57,7 +57,7 @@ GATES = (
     "dgrad.cout1.res_mode", "dgrad.cout1.Cout", "dgrad.p2.tiles", "dgrad.p2.Cout%16", "dgrad.p2.odd.Cout>=64", "dgrad.p2.mask_bf16",
     "dgrad.p2.add", "dgrad.p2.stride", "dgrad.ride.env", "dgrad.ride.p2", "dgrad.thin.pixels", "dgrad.patch.tiles512",
     "dgrad.s2.phase",
-    # conv_wgrad / wgrad_tr_try / hrv_conv2d_wgrad_s2_supported
+    # conv_wgrad / hrv_conv2d_wgrad_route (wgrad_route, wgrad_tr_class, wgrad_s2_class)
     "wgrad.cout1.Cout", "wgrad.tr.pixels", "wgrad.tr.W>=32", "wgrad.tr.W>=32.odd", "wgrad.tr.x_granule", "wgrad.tr.dy_granule", "wgrad.s2.x_granule",
     "wgrad.tr.Cout%64", "wgrad.tr.Cp", "wgrad.tr.min_pix_env", "wgrad.tr.env",
     "wgrad.tr.x_up", "wgrad.tr.storage", "wgrad.s2.pixels", "wgrad.s2.Wo>=32", "wgrad.s2.Cout%128", "wgrad.s2.env",
@@ -75,9 +75,9 @@ NOT_WALKED = {
     "residual/add_after.data_ptr() % 16": "torch allocations are 256-byte aligned: the far side cannot be built without pointer surgery",
     "wgrad_s2 slab extent (31-bit offsets)": "needs one slab of >= 2 GiB: with Cout = 8192 (one slab) and X as a 64-channel slice of a "
                                              "16384-channel tensor, X alone is 2.1 GB and the float64 reference 279 GFLOP; not reachable at "
-                                             "test size.  The check now sits in hrv_conv2d_wgrad_s2_supported itself (one predicate, asked by "
-                                             "both halves), so there is no accept-then-decline window left to test.",
-    "wgrad_tr slab extent (31-bit offsets)": "as above; part of hrv_conv2d_wgrad_tr_supported",
+                                             "test size.  The check sits in wgrad_s2_class, which hrv_conv2d_wgrad_route and the launch both answer "
+                                             "from (one predicate), so there is no accept-then-decline window left to test.",
+    "wgrad_tr slab extent (31-bit offsets)": "as above; part of wgrad_tr_class",
     "cin <= 2048 (_cout1_ok)": "a 2052-channel fp32 source: no layer shape, and the far side is the generic engine already covered",
     "HRV_CONV_P2_WIDE=0, HRV_CONV_PATCHW, HRV_CONV_PATCH=16, HRV_CONV_TILE_TRAIN": "A/B and test knobs, off by default",
 }

@@ -211,13 +211,32 @@ def test_conv_s2_host_logic(lib):
     assert sup(0, 64, 128, 0, 8, 257, 193) == 1 and sup(0, 48, 128, 0, 8, 257, 193) == 0      # a forward chunk lies in one sub-pixel
     assert sup(1, 128, 256, 64, 4, 513, 385) == 1 and sup(1, 128, 256, 48, 4, 513, 385) == 0   # a column tile lies in one phase
     assert sup(0, 64, 128, 0, 1, 9, 9) == 0                                                     # too few tiles for the persistent grid
-    ws = lib.hrv_conv2d_wgrad_s2_supported
+    # hrv_conv2d_wgrad_route over a descriptor with bf16-stored operands, mma_bf16 = 1, x_up_shift = 0 and the matching Ho / Wo (what
+    # plan_wgrad asks, and what hrv_conv2d_wgrad launches by): ws -> 1 where wgrad_s2.hip serves the 4x4 stride-2 pad-2 layer,
+    # wt -> 1 + the shape class wgrad_tr.hip takes for the stride-1 'same' layer, 0 where the generic bf16 kernel runs
+    assert C.sizeof(_lib.hrv_conv2d_wgrad_t) == 144     # 2 x (ptr + 4 x i32) | 14 x i32 | ptr + i64 + 2 ptr | 2 x i32
+
+    def route(Cout, x_C, x_cstride, x_coff, dy_cstride, dy_coff, N, H, W, KH, KW, stride, pad, Ho, Wo, **kw):
+        d = _lib.hrv_conv2d_wgrad_t(Cout=Cout, x_C=x_C, x_cstride=x_cstride, x_coff=x_coff, dy_cstride=dy_cstride, dy_coff=dy_coff,
+                                    x_C_real=x_C, CinTot=x_C, N=N, H=H, W=W, Ho=Ho, Wo=Wo, KH=KH, KW=KW, stride=stride, pad=pad,
+                                    mma_bf16=1, storage_flags=3)
+        for k, v in kw.items():
+            setattr(d, k, v)
+        return lib.hrv_conv2d_wgrad_route(C.byref(d))
+
+    def ws(Cout, x_C, x_cstride, x_coff, dy_cstride, dy_coff, N, H, W):
+        r = route(Cout, x_C, x_cstride, x_coff, dy_cstride, dy_coff, N, H, W, 4, 4, 2, 2, H // 2 + 1, W // 2 + 1)
+        assert r in (_lib.WGRAD_S2, _lib.WGRAD_BF16), r
+        return 1 if r == _lib.WGRAD_S2 else 0
+
+    def wt(Cout, x_C, x_cstride, x_coff, dy_cstride, dy_coff, N, H, W, KH, KW, pad):
+        r = route(Cout, x_C, x_cstride, x_coff, dy_cstride, dy_coff, N, H, W, KH, KW, 1, pad, H, W)
+        assert r == _lib.WGRAD_BF16 or _lib.WGRAD_TR <= r <= _lib.WGRAD_TR + 8, r
+        return r - _lib.WGRAD_TR + 1 if r >= _lib.WGRAD_TR else 0
+
     assert ws(128, 64, 64, 0, 128, 0, 8, 513, 385) == 1 and ws(256, 128, 128, 0, 256, 0, 8, 257, 193) == 1
     assert ws(128, 64, 192, 0, 128, 0, 8, 257, 193) == 1          # X as the hi third of a split tensor
     assert ws(96, 64, 64, 0, 96, 0, 8, 513, 385) == 0 and ws(128, 64, 64, 0, 128, 0, 1, 33, 33) == 0
-    # hrv_conv2d_wgrad_tr_supported(Cout, x_C, x_cstride, x_coff, dy_cstride, dy_coff, N, H, W, KH, KW, pad): 1 + the class
-    # wgrad_tr_try will take, 0 where it declines (train_ops.conv_wgrad pads a bf16 dY for the fallback kernel then)
-    wt = lib.hrv_conv2d_wgrad_tr_supported
     assert wt(256, 128, 128, 0, 256, 0, 4, 128, 96, 3, 3, 1) == 1 and wt(64, 144, 144, 0, 64, 0, 4, 256, 192, 3, 3, 1) == 5
     assert wt(64, 48, 48, 0, 64, 0, 4, 513, 385, 2, 2, 1) == 9                     # PatchGAN's model0 over its space-to-depth image
     assert wt(64, 48, 48, 0, 64, 0, 1, 280, 30, 2, 2, 1) == 0                      # W < 32: 8400 pixels are not enough
@@ -229,3 +248,18 @@ def test_conv_s2_host_logic(lib):
     assert wt(64, 48, 48, 0, 64, 0, 1, 64, 127, 2, 2, 1) == 0 and wt(64, 48, 48, 0, 64, 0, 1, 64, 128, 2, 2, 1) == 9      # N*H*W >= 8192
     assert wt(60, 64, 64, 0, 64, 0, 1, 64, 128, 3, 3, 1) == 0 and wt(64, 64, 64, 4, 64, 0, 1, 64, 128, 3, 3, 1) == 0     # Cout % 64, granule
     assert wt(64, 64, 64, 0, 64, 0, 1, 64, 128, 3, 3, 0) == 0 and wt(64, 64, 64, 0, 64, 0, 1, 64, 128, 4, 4, 2) == 0     # 'same' 1x1..3x3 only
+    # the front conditions (only Python could answer these before): the accepted shape 64 -> 64, 1 x 64 x 128, 3x3 pad 1 (class 5)
+    # falls to the generic bf16 kernel with a resampled X, with an fp32 dY, and where dY is not the 'same' extent
+    base = (64, 64, 64, 0, 64, 0, 1, 64, 128, 3, 3, 1, 1)
+    assert route(*base, 64, 128) == _lib.WGRAD_TR + 5
+    assert route(*base, 64, 128, x_up_shift=1) == _lib.WGRAD_BF16
+    assert route(*base, 64, 128, storage_flags=2) == _lib.WGRAD_BF16
+    assert route(64, 64, 64, 0, 64, 0, 1, 64, 128, 3, 3, 1, 0, 62, 126) == _lib.WGRAD_BF16
+    # the other codes, the storage forms that are errors by contract, and an s2 shape whose Ho is not H / 2 + 1
+    assert route(*base, 64, 128, mma_bf16=0, storage_flags=0) == _lib.WGRAD_F32
+    assert route(*base, 64, 128, storage_flags=0) == _lib.WGRAD_BF16
+    assert route(*base, 64, 128, storage_flags=1) < 0 and route(*base, 64, 128, mma_bf16=0, storage_flags=3) < 0
+    assert route(*base, 64, 128, storage_flags=4) < 0
+    assert route(128, 64, 64, 0, 128, 0, 8, 513, 385, 4, 4, 2, 2, 257, 193) == _lib.WGRAD_S2
+    assert route(128, 64, 64, 0, 128, 0, 8, 513, 385, 4, 4, 2, 2, 256, 193) == _lib.WGRAD_BF16
+    assert route(128, 64, 64, 0, 128, 0, 8, 513, 385, 4, 4, 2, 2, 257, 192) == _lib.WGRAD_BF16

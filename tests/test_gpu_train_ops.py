@@ -365,7 +365,7 @@ def test_mixed_precision_conv_forward_and_dgrad(case):
                                   ("patchgan_odd_s2", 12, 64, 4, 2, 2, 40, 96), ("patchgan_odd_s1", 32, 8, 4, 1, 2, 20, 33)],
                          ids=lambda c: c[0])
 def test_mixed_precision_wgrad(case):
-    """hrv_conv2d_wgrad_bf16mma_nhwc_f32 (quad-transposed staging, v_mfma_f32_32x32x16_bf16) vs the fp32 weight
+    """hrv_conv2d_wgrad with mma_bf16 (quad-transposed staging, v_mfma_f32_32x32x16_bf16) vs the fp32 weight
     gradient of the bf16-rounded operands.  The odd-width cases (PatchGAN 4x4 convolutions: Wo = W/2 + 1) reach the kernel
     through a zero-padded dY (conv_wgrad)."""
     ops, T = _mods()
@@ -427,7 +427,7 @@ def test_mixed_precision_bf16_stored_operands_are_bit_identical(case, dy_bf16):
     """Tensors that only matrix cores read may be STORED in bf16 by the mixed-precision plan (actv, the expanded
     label map, [dgamma|dbeta]).  The MMA operand bits are then the same as when the fp32 tensor is rounded while
     staged, so every consumer -- forward conv, data gradient (bf16 source / bf16 sign mask), weight gradient incl.
-    the fused bias column (hrv_conv2d_wgrad_bf16mma_st_nhwc_f32, packed staging) -- gives BIT-IDENTICAL results."""
+    the fused bias column (hrv_conv2d_wgrad with storage_flags, packed staging) -- gives BIT-IDENTICAL results."""
     ops, T = _mods()
     name, cin, cout, k, pad, H, W = case
     g = torch.Generator().manual_seed(cin + cout)
