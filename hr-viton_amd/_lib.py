@@ -174,6 +174,16 @@ class hrv_lpips_tap_t(C.Structure):
                 ("HW", C.c_int32), ("C", C.c_int32), ("cstride", C.c_int32), ("_pad", C.c_int32)]
 
 
+HRV_VIZ_MAX_PANELS, HRV_VIZ_MAX_CLASSES = 16, 20
+VIZ_SIGNED, VIZ_UNIT, VIZ_SEGMAP = 0, 1, 2      # hrv_viz_panel_t.kind
+VIZ_ROUND, VIZ_TRUNC = 0, 1                     # hrv_viz_grid_u8's quant
+
+
+class hrv_viz_panel_t(C.Structure):
+    _fields_ = [("ptr", C.c_void_p), ("sn", C.c_int64), ("sy", C.c_int64), ("sx", C.c_int64), ("sc", C.c_int64),
+                ("C", C.c_int32), ("kind", C.c_int32)]
+
+
 # every symbol include/hrviton_hip.h declares: (restype, argtypes)
 _i32, _i64, _f, _vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
 _ip = C.POINTER(C.c_int32)
@@ -339,6 +349,7 @@ SYMBOLS = {
     "hrv_seg_iou_nchw_f32": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "hrv_lpips_prep_resize_nchw_f32": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_float),
                                                  C.POINTER(C.c_float), _vp, _vp]),
+    "hrv_viz_grid_u8": (C.c_int, [C.POINTER(hrv_viz_panel_t), _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
 }
 
 _lib = None

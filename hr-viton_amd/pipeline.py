@@ -2,7 +2,7 @@
 ``test()`` loop (test_generator.py:118-219) without its host round trips."""
 from __future__ import annotations
 
-from typing import Dict
+from typing import Dict, Optional
 
 import torch
 
@@ -35,17 +35,21 @@ def tryon_step(opt, tocg, generator, inputs: Dict[str, torch.Tensor], noise=None
     output = generator(x, parse7, noise=noise) if noise is not None else generator(x, parse7)
     return {"output": output, "warped_cloth": warped_cloth, "warped_clothmask": warped_clothmask,
             "fake_parse_gauss": gauss, "fake_parse": labels, "parse": parse7, "flow_list": flow_list,
-            "fake_segmap": fake_segmap}
+            "fake_segmap": fake_segmap, "pre_clothes_mask": pre_clothes_mask}
 
 
-def make_generator_inputs(opt, tocg, inputs: Dict[str, torch.Tensor]):
+def make_generator_inputs(opt, tocg, inputs: Dict[str, torch.Tensor], aux: Optional[dict] = None):
     """train_generator.py:201-275 (the no_grad block): frozen tocg at 256x192 -> parse glue ->
-    high-resolution cloth warp.  Returns (x [N,9,H,W], parse7 Act)."""
+    high-resolution cloth warp.  Returns (x [N,9,H,W], parse7 Act).  ``aux``: a dictionary that receives what the reference's
+    recording block shows (:366-369) -- 'cm' (the binarised cloth mask), 'warped_cloth' (the view x[:, 6:9]) and 'fake_parse_gauss'
+    (NHWC Act; under --GT the ground-truth parse map, NCHW); the default None leaves the function as it is."""
     if getattr(opt, "GT", False):
         # --GT (train_generator.py:253-256): ground-truth parse map and ground-truth warped cloth, no tocg
         with torch.no_grad():
             _, parse7 = glue.parse_from_scores(inputs["parse"])
             x = torch.cat((inputs["agnostic"], inputs["densepose"], inputs["parse_cloth"]), dim=1)
+        if aux is not None:
+            aux.update(warped_cloth=x[:, 6:9], fake_parse_gauss=inputs["parse"])
         return x, parse7
     with torch.no_grad():
         c_paired, pose, agnostic = inputs["cloth"], inputs["densepose"], inputs["agnostic"]
@@ -62,12 +66,15 @@ def make_generator_inputs(opt, tocg, inputs: Dict[str, torch.Tensor]):
         if getattr(opt, "occlusion", False):
             glue.occlusion(gauss, warped)
         x = torch.cat((agnostic, pose, ops.to_nchw(warped, 0, 3)), dim=1)    # :279
+    if aux is not None:
+        aux.update(cm=cm, warped_cloth=x[:, 6:9], fake_parse_gauss=gauss)
     return x, parse7
 
 
 def generator_train_step(opt, generator, discriminator, crit_gan, crit_feat, crit_vgg, opt_g, opt_d, x, parse7, im,
-                         sync_g=None, sync_d=None, noise=None, noise_d=None):
-    """One G step + one D step of train_generator.py:279-360.  ``parse7``: Act [N,H,W,8] (7 real).
+                         sync_g=None, sync_d=None, noise=None, noise_d=None, aux: Optional[dict] = None):
+    """One G step + one D step of train_generator.py:279-360.  ``parse7``: Act [N,H,W,8] (7 real).  ``aux``: a dictionary that
+    receives 'output', the D step's generator output, which is what the reference's recording block shows (:368).
     ``noise`` / ``noise_d``: the SPADE noise draws of the two generator forwards (default: drawn like the reference,
     network_generator.py:104-107); the data-parallel equivalence test injects them."""
     pair = hasattr(discriminator, "forward_pair") and not getattr(opt, "_hrv_no_pair", False)
@@ -109,6 +116,8 @@ def generator_train_step(opt, generator, discriminator, crit_gan, crit_feat, cri
         sync_d.begin()
     with torch.no_grad():
         output = generator(x, parse7, noise=noise_d)       # new noise, post-update weights (:327-330)
+    if aux is not None:
+        aux["output"] = output
     if pair:
         pred_fake, pred_real = discriminator.forward_pair(parse7, output, im)
     else:
@@ -131,13 +140,15 @@ def remove_overlap(seg_out, warped_cm):
 
 
 def condition_train_step(opt, tocg, D, crit_l1, crit_vgg, crit_gan, opt_g, opt_d, inputs: Dict[str, torch.Tensor],
-                         sync_g=None, sync_d=None):
+                         sync_g=None, sync_d=None, aux: Optional[dict] = None):
     """One iteration of train_condition.py:136-286 (the default `not G_D_seperate` order): tocg forward with
     batch-statistics BatchNorm, warping / TV / interflow / cross-entropy / LSGAN losses, G step, D step.
     The networks, warps, softmax, cross entropy, TV, L1, VGG and LSGAN terms run on the HIP kernels
     (cond_train.py, functional.py, losses.py, vgg.py); torch only stitches the scalar sums and the
     elementwise mask compositions.  ``inputs`` as produced by cp_dataset.py: cloth, cloth_mask,
-    parse_agnostic, densepose, parse_onehot (label indices [N,1,H,W]), parse (one-hot), pcm, parse_cloth.
+    parse_agnostic, densepose, parse_onehot (label indices [N,1,H,W]), parse (one-hot), pcm, parse_cloth.  ``aux``: a dictionary that
+    receives what the reference's recording block shows (:377-380), detached -- 'cm_paired', the composed 'fake_segmap',
+    'warped_cloth', the thresholded 'warped_cm_onehot' and 'misalign' (float); the default None leaves the function as it is.
 
     Stated deviations from the reference's schedule (same losses, gradients and updates per iteration):
     * the reference calls D three times before either optimizer step (G pass, fake, real: :262-274); here the fake and
@@ -159,6 +170,8 @@ def condition_train_step(opt, tocg, D, crit_l1, crit_vgg, crit_gan, opt_g, opt_d
     if sync_d is not None:
         sync_d.enabled = False          # D's gradients of loss_G are discarded by optimizer_D.zero_grad() (:284)
     flow_list, fake_segmap, warped_cloth, warped_cm = tocg(input1, input2)      # :158
+    # (:162 thresholds the mask before --occlusion's remove_overlap rebinds the name)
+    flow_warped_cm = warped_cm.detach() if aux is not None else None
     comp = getattr(opt, "clothmask_composition", "warp_grad")
     if comp != "no_composition":                                               # :164-173
         cloth_mask = torch.ones_like(fake_segmap.detach())
@@ -167,6 +180,12 @@ def condition_train_step(opt, tocg, D, crit_l1, crit_vgg, crit_gan, opt_g, opt_d
     if getattr(opt, "occlusion", False):                                       # :174-176
         warped_cm = remove_overlap(HF.softmax(fake_segmap, dim=1), warped_cm)
         warped_cloth = warped_cloth * warped_cm + torch.ones_like(warped_cloth) * (1 - warped_cm)
+    if aux is not None:                                                        # :162,179-181
+        with torch.no_grad():
+            onehot = (flow_warped_cm > 0.5).to(torch.float32)
+            fake_clothmask = (torch.argmax(fake_segmap.detach(), dim=1, keepdim=True) == 3).to(torch.float32)
+            aux.update(cm_paired=cm_paired, fake_segmap=fake_segmap.detach(), warped_cloth=warped_cloth.detach(),
+                       warped_cm_onehot=onehot, misalign=(fake_clothmask - onehot).clamp_min_(0))
     loss_l1_cloth = crit_l1(warped_cm, pcm)                                    # :184
     use_vgg = crit_vgg is not None
     loss_vgg = crit_vgg(warped_cloth, im_c) if use_vgg else torch.zeros((), device=c_paired.device)   # :185

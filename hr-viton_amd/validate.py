@@ -20,7 +20,8 @@ Stated deviations from the reference:
   reference.
 * Under data-parallel training rank 0 evaluates and the other ranks wait in their next gradient all-reduce; sharding the pass is
   out of scope.
-* The tensorboard image grids (``visualize_segmap``, ``make_image_grid``) are out of scope.
+* The tensorboard image grids (``visualize_segmap``, ``make_image_grid``) and loss scalars are not part of these passes: the
+  scripts record them under ``--board`` through hr_viton_amd.viz (``BoardLog`` extends ``ScalarLog``).
 """
 from __future__ import annotations
 
@@ -134,12 +135,17 @@ class ScalarLog(object):
         os.makedirs(self.dir, exist_ok=True)
         with open(self.path, "a") as f:
             f.write(json.dumps({"tag": tag, "value": float(value), "step": int(step)}) + "\n")
+        board = self._writer()
+        if board is not None:
+            board.add_scalar(tag, float(value), int(step))
+
+    def _writer(self):
+        """The run's SummaryWriter, made at the first record; None where neither package imports."""
         if not self._board_tried:
             self._board_tried = True
             cls = _summary_writer_class()
             self._board = cls(log_dir=self.dir) if cls is not None else None
-        if self._board is not None:
-            self._board.add_scalar(tag, float(value), int(step))
+        return self._board
 
     def close(self):
         if self._board is not None:

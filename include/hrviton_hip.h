@@ -977,6 +977,34 @@ int hrv_seg_iou_nchw_f32(const float* seg, const float* cm, const float* label, 
 int hrv_lpips_prep_resize_nchw_f32(const float* in0, const float* in1, int32_t N, int32_t H, int32_t W, int32_t Ho, int32_t Wo,
                                    int32_t normalize, const float* shift3, const float* scale3, float* out, hrv_stream_t stream);
 
+/* ---- image grids of the scripts (viz.py; viz.hip) ---- */
+#define HRV_VIZ_MAX_PANELS 16
+#define HRV_VIZ_MAX_CLASSES 20
+enum { HRV_VIZ_SIGNED = 0, HRV_VIZ_UNIT = 1, HRV_VIZ_SEGMAP = 2 };   /* hrv_viz_panel_t.kind */
+enum { HRV_VIZ_ROUND = 0, HRV_VIZ_TRUNC = 1 };                       /* quant */
+/* One panel of a grid: an fp32 view of N x H x W pixels with C channels, addressed in ELEMENTS as
+ * ptr[n * sn + y * sy + x * sx + c * sc] -- NCHW tensors and channel slices of them, NHWC slices, a mask broadcast over the channels
+ * (sc == 0) and one sample shown in every grid (sn == 0) need no copy.  kind SIGNED: v = x * 0.5 + 0.5; UNIT: v = x (both C == 3,
+ * or C == 1: the one channel is shown as grey); SEGMAP: the index of the first maximum over the C channels (1 <= C <= 20, as
+ * np.argmax), shown in the 20-colour palette of the reference's utils.visualize_segmap.  Where sc == 1, ptr is 16-byte aligned and
+ * sn, sy, sx are multiples of 4, a pixel is read as float4 groups: the C channels rounded up to a multiple of 4 must then be
+ * readable (an NHWC tensor whose channel stride is a multiple of 4); what lies behind channel C - 1 is never looked at. */
+typedef struct {
+  const float* ptr;
+  int64_t sn, sy, sx, sc;
+  int32_t C;
+  int32_t kind;
+} hrv_viz_panel_t;
+/* N grids of `npanels` panels in one launch: out uint8 [N,Hg,Wg,3] (4-byte aligned), laid out as torchvision's make_grid with
+ * pad_value 0 does: xmaps = min(nrow, npanels), ymaps = ceil(npanels / xmaps), Hg = ymaps * (H + padding) + padding, Wg = xmaps *
+ * (W + padding) + padding, panel k at row (k / xmaps) * (H + padding) + padding, column (k % xmaps) * (W + padding) + padding;
+ * borders and the unfilled cells of the last row are 0; npanels == 1 gives the bare panel [N,H,W,3].  SIGNED / UNIT values become
+ * bytes by quant ROUND: (uint8) clamp(v * 255 + 0.5, 0, 255) with the product and the sum rounded separately (torchvision
+ * save_image; not round-half-even), or TRUNC: (uint8) clamp(v * 255, 0, 255) (utils.save_images, tensorboard); SEGMAP bytes are the
+ * palette's.  Inputs are assumed finite.  `panels` is a host array: it travels in the kernel arguments. */
+int hrv_viz_grid_u8(const hrv_viz_panel_t* panels, int32_t npanels, int32_t nrow, int32_t padding, int32_t N, int32_t H, int32_t W,
+                    int32_t quant, uint8_t* out, hrv_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,6 @@
 """Evaluation micro-benchmark (evaluate.py's GPU work, csrc/metrics.hip + AlexNet on the fp32 conv engine).
 
-  python tools/eval_bench.py [--pairs B] [--reps R] [--e2e N] [--out DIR]
+  python tools/eval_bench.py [--pairs B] [--reps R] [--e2e N] [--out DIR] [--only viz]
 
 1. pair statistics (gray + SSIM + SSE) on B synthetic device-resident 1024x768 RGB pairs: event time per pair and the fraction
    of the larger of two floors -- bytes (both uint8 images read once, at the measured 6.29 TB/s copy rate) and VALU FLOPs (the
@@ -20,6 +20,11 @@
    feature banks of 2032 x 2048 (the size of a VITON-HD test set): ``moments`` (mean, centre-and-transpose, the symmetric fp64
    covariance GEMM: 2 x 2048^2 x 2032 / 2 FLOPs computed), one ``poly_gram`` of 2032 x 2032 x 2048, both as TFLOP/s of fp64 over
    event time, KID's subset sums for 100 subsets of 1000, and the host's Frechet distance (two 2048 x 2048 ``eigh``) in wall time.
+7. the image grids (csrc/viz.hip, ``--only viz`` runs this section alone): ``viz.grid_u8`` over the 12 panels of the try-on grid at
+   1024x768, N = 1 and 4 -- event time of the launch, the GB/s of its algorithmic bytes (every source element once, every output
+   byte once) against the copy rate, and the wall time including the uint8 copy to the host -- next to the host path measured in
+   the same process: the fp32 panels copied to the host and composed there as the reference does (argmax + PIL palette, make_grid,
+   mul(255).add(0.5).clamp).  The same for ``save_images``' quantise-and-copy at 1024x768, batch 16, against the host expression.
 Event times include launch gaps; for kernel-only times run this under ``rocprofv3 --kernel-trace --stats`` in a run of its own.
 Prints one JSON line.
 """
@@ -165,6 +170,88 @@ def validation_bench(B, reps):
     return out
 
 
+def _wall(fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / reps
+
+
+def _host_visualize_segmap(x, batch, palette):
+    from PIL import Image
+    im = Image.fromarray(np.argmax(x[batch].float().numpy(), axis=0).astype(np.uint8), "P")
+    im.putpalette(palette)
+    return torch.from_numpy(np.array(im.convert("RGB"))).permute(2, 0, 1).float().div(255)
+
+
+def _host_make_grid(ts, nrow, pad=2):
+    t = torch.stack(ts)
+    n, _, H, W = t.shape
+    xm = min(nrow, n)
+    ym = -(-n // xm)
+    g = t.new_zeros((3, ym * (H + pad) + pad, xm * (W + pad) + pad))
+    for k in range(n):
+        y0, x0 = (k // xm) * (H + pad) + pad, (k % xm) * (W + pad) + pad
+        g[:, y0:y0 + H, x0:x0 + W].copy_(t[k])
+    return g
+
+
+def viz_bench(reps, H=1024, W=768):
+    """Section 7.  The comparator is the reference's own path (test_generator.py:223-229, utils.py:93-109) on CPU tensors, never
+    the code under test."""
+    from hr_viton_amd import viz
+    g = torch.Generator(device="cuda").manual_seed(4)
+    out = {"tryon_grid_1024x768": {}}
+    for N in (1, 4):
+        u = lambda c: torch.rand(N, c, H, W, device="cuda", generator=g) * 2 - 1  # noqa: E731
+        inputs = {"cloth": u(3), "parse_agnostic": u(13), "densepose": u(3), "pose": u(3), "agnostic": u(3), "image": u(3)}
+        gauss = ops.alloc(N, H, W, 13, "cuda")
+        gauss.t.copy_(torch.rand(N, H, W, 16, device="cuda", generator=g))
+        res = {"pre_clothes_mask": (u(1) > 0).float(), "warped_cloth": u(3), "warped_clothmask": u(1) * 0.5 + 0.5,
+               "fake_parse_gauss": gauss, "output": u(3)}
+        src_bytes = 4.0 * N * H * W * (3 * 8 + 1 * 2 + 13 + 16)       # 8 colour panels, 2 masks, 13 planes, 4 float4 per NHWC pixel
+        res_ref = dict(res, fake_parse_gauss=ops.to_nchw(gauss))    # the reference holds it NCHW on the device: not timed
+        grid = viz.tryon_grid(inputs, res)
+        nbytes = src_bytes + grid.numel()
+        t_k = timed(lambda: viz.tryon_grid(inputs, res), reps)
+        t_e2e = _wall(lambda: viz.to_host(viz.tryon_grid(inputs, res)), reps)
+
+        def host_path():
+            cpu = {k: v.cpu() for k, v in inputs.items()}
+            r = {k: v.cpu() for k, v in res_ref.items()}
+            grids = []
+            for i in range(N):
+                seg = lambda t: _host_visualize_segmap(t, i, viz.PALETTE)  # noqa: E731
+                grids.append(_host_make_grid(
+                    [cpu["cloth"][i] / 2 + 0.5, r["pre_clothes_mask"][i].expand(3, -1, -1), seg(cpu["parse_agnostic"]),
+                     (cpu["densepose"][i] + 1) / 2, r["warped_cloth"][i] / 2 + 0.5, r["warped_clothmask"][i].expand(3, -1, -1),
+                     seg(r["fake_parse_gauss"]), cpu["pose"][i] / 2 + 0.5, r["warped_cloth"][i] / 2 + 0.5, cpu["agnostic"][i] / 2 + 0.5,
+                     cpu["image"][i] / 2 + 0.5, r["output"][i] / 2 + 0.5], 4).mul(255).add_(0.5).clamp_(0, 255).permute(1, 2, 0)
+                    .to(torch.uint8))
+            return grids
+
+        t_host = _wall(host_path, max(1, reps // 10))
+        same = all(torch.equal(a, b) for a, b in zip(host_path(), viz.tryon_grid(inputs, res).cpu()))
+        out["tryon_grid_1024x768"][f"N_{N}"] = {
+            "kernel_us": 1e6 * t_k, "gb_per_s": nbytes / t_k / 1e9, "fraction_of_copy_rate": nbytes / t_k / HBM_BPS,
+            "device_path_with_u8_copy_ms": 1e3 * t_e2e, "host_path_ms": 1e3 * t_host, "host_over_device": t_host / t_e2e,
+            "bytes_equal": bool(same)}
+    B = 16
+    img = torch.rand(B, 3, H, W, device="cuda", generator=g) * 2.4 - 1.2
+    t_k = timed(lambda: viz.quantize_images(img), reps)
+    t_e2e = _wall(lambda: viz.to_host(viz.quantize_images(img)), reps)
+    host = lambda: [((t.clone() + 1) * 0.5 * 255).cpu().clamp(0, 255).numpy().astype("uint8") for t in img]  # noqa: E731
+    t_host = _wall(host, max(1, reps // 10))
+    nbytes = 5.0 * B * H * W * 3                                   # 4 bytes in + 1 byte out per element
+    out["save_images_1024x768_b16"] = {
+        "kernel_us": 1e6 * t_k, "gb_per_s": nbytes / t_k / 1e9, "fraction_of_copy_rate": nbytes / t_k / HBM_BPS,
+        "quantise_and_copy_ms": 1e3 * t_e2e, "host_path_ms": 1e3 * t_host, "host_over_device": t_host / t_e2e}
+    return out
+
+
 def e2e(n, workers, batch):
     from PIL import Image
     rng = np.random.default_rng(0)
@@ -199,7 +286,16 @@ def main():
     ap.add_argument("--e2e", type=int, default=64, help="pairs of the evaluate.py run (0: skip)")
     ap.add_argument("--workers", type=int, default=8)
     ap.add_argument("--out", default="")
+    ap.add_argument("--only", default="", choices=["", "viz"], help="run one section alone")
     a = ap.parse_args()
+    if a.only == "viz":
+        res = {"viz": viz_bench(a.reps)}
+        print(json.dumps(res))
+        if a.out:
+            os.makedirs(a.out, exist_ok=True)
+            with open(os.path.join(a.out, "eval_bench_viz.json"), "w") as f:
+                json.dump(res, f, indent=1)
+        return
     B, H, W = a.pairs, 1024, 768
     g = torch.Generator(device="cuda").manual_seed(0)
     gt = torch.randint(0, 256, (B, H, W, 3), dtype=torch.uint8, device="cuda", generator=g)
@@ -215,7 +311,8 @@ def main():
                           "byte_floor_ms_per_pair": 1e3 * fb / B, "valu_floor_ms_per_pair": 1e3 * ff / B,
                           "fraction_of_floor": floor / t_ps},
            "lpips_128": {"B": B, "ms_per_pair": 1e3 * t_lp / B},
-           "inception_299": inception_bench(B, a.reps), "validation": validation_bench(B, a.reps), "fid": fid_bench(B, a.reps)}
+           "inception_299": inception_bench(B, a.reps), "validation": validation_bench(B, a.reps), "fid": fid_bench(B, a.reps),
+           "viz": viz_bench(a.reps)}
     if a.e2e:
         res["evaluate_py"] = e2e(a.e2e, a.workers, B)
     print(json.dumps(res))

@@ -13,8 +13,15 @@ kernels (hr_viton_amd.cond_train, .functional, .losses, .vgg); one iteration is
   * validation (train_condition.py:313-360): every ``--val_count`` steps rank 0 scores the first ``--val_items`` items of the test
     list (``--test_dataroot`` / ``--test_data_list``; fixed-seed synthetic batches under ``--synthetic``) with tocg in eval mode and
     logs ``val/iou`` to ``<tensorboard_dir>/<name>/scalars.jsonl`` (and to tensorboard where a SummaryWriter is importable):
-    hr_viton_amd.validate, which states the deviations.  The tensorboard loss scalars and image grids (``visualize_segmap``,
-    :362-418) are out of scope.
+    hr_viton_amd.validate, which states the deviations.
+  * recording (train_condition.py:362-436) is opt-in: with ``--board`` rank 0 records, every ``--tensorboard_count`` steps, the loss
+    scalars under the reference's tags (``Loss/G``, ``Loss/G/l1_cloth``, ``Loss/G/vgg``, ``Loss/G/tv``, ``Loss/G/CE``, ``Loss/G/GAN``,
+    ``Loss/D``, ``Loss/D/pred_real``, ``Loss/D/pred_fake``; a term that is switched off is skipped) into ``scalars.jsonl``, and the
+    12-panel grids ``train_images`` and -- unless ``--no_test_visualize`` -- ``test_images/{i}``, i < ``--num_test_visualize`` (tocg
+    in eval mode on test items) as PNGs under ``<tensorboard_dir>/<name>/images/``: ``visualize_segmap``, ``make_grid`` and the
+    quantisation run in one HIP launch (hr_viton_amd.viz, which states the deviations).  Without ``--board`` nothing of this is
+    computed or written and ``--tensorboard_count`` is ignored.  Writing tensorboard event files without a SummaryWriter package
+    is out of scope.
   * --warp_feature encoder / --out_layer conv (networks.py:46-61,142-144) and --upsample nearest (the inter-flow loss's flow
     resize, train_condition.py:242 -- the only place the reference's scripts use the flag) are on the HIP path (round 5).
 """
@@ -32,6 +39,7 @@ if ROOT not in sys.path:
 
 import hr_viton_amd  # noqa: E402,F401
 from hr_viton_amd import dist as hdist  # noqa: E402
+from hr_viton_amd import viz  # noqa: E402
 from hr_viton_amd.gen_train import attach_grad_sync  # noqa: E402
 from hr_viton_amd.losses import L1Loss  # noqa: E402
 from hr_viton_amd.networks import (ConditionGenerator, GANLoss, VGGLoss, define_D, load_checkpoint,  # noqa: E402
@@ -39,7 +47,7 @@ from hr_viton_amd.networks import (ConditionGenerator, GANLoss, VGGLoss, define_
 from hr_viton_amd.optim import Adam  # noqa: E402
 from hr_viton_amd.parallel import broadcast_module  # noqa: E402
 from hr_viton_amd.pipeline import condition_train_step  # noqa: E402
-from hr_viton_amd.validate import ScalarLog, condition_validation_iou, val_items_loader, validation_due  # noqa: E402
+from hr_viton_amd.validate import condition_validation_iou, val_items_loader, validation_due  # noqa: E402
 
 
 def get_opt(argv=None):
@@ -103,6 +111,8 @@ def get_opt(argv=None):
                    help="plumbing / bench runs only: a RANDOMLY initialised VGG19 in the perceptual loss (no network here to "
                         "download the pretrained weights); implied by --synthetic")
     p.add_argument("--val_items", type=int, default=2000, help="test items scored per val/iou pass (the reference's 2000)")
+    p.add_argument("--board", action="store_true",
+                   help="every --tensorboard_count steps record the loss scalars and the image grids (train_condition.py:362-436)")
     opt = p.parse_args(argv)
     return opt
 
@@ -123,6 +133,13 @@ def synthetic_batch(opt, n, seed, device):
     return {k: v.to(device) for k, v in b.items()}
 
 
+def synthetic_image(opt, n, seed, device):
+    """The 'image' entry of a synthetic batch (only the grids show it), from a generator of its own: the draws of
+    ``synthetic_batch`` stay what they are."""
+    g = torch.Generator().manual_seed(seed + 500_009)
+    return (torch.rand(n, 3, opt.fine_height, opt.fine_width, generator=g) * 2 - 1).to(device)
+
+
 def _rank_loader(opt, per_rank, rank, world):
     """CPDataset over the reference's on-disk layout; every rank draws its own shuffled stream of per_rank samples."""
     import copy
@@ -133,15 +150,18 @@ def _rank_loader(opt, per_rank, rank, world):
     return CPDataLoader(o, CPDataset(o), rank, world)
 
 
-def disk_batch(inputs, device):
+def disk_batch(inputs, device, datasetting="paired"):
     """cp_dataset.py batch -> the flat dictionary condition_train_step takes (train_condition.py:136-153)."""
-    return {"cloth": inputs["cloth"]["paired"].to(device), "cloth_mask": inputs["cloth_mask"]["paired"].to(device),
+    return {"cloth": inputs["cloth"][datasetting].to(device), "cloth_mask": inputs["cloth_mask"][datasetting].to(device),
             "parse_agnostic": inputs["parse_agnostic"].to(device), "densepose": inputs["densepose"].to(device),
             "parse_onehot": inputs["parse_onehot"].to(device), "parse": inputs["parse"].to(device),
             "pcm": inputs["pcm"].to(device), "parse_cloth": inputs["parse_cloth"].to(device)}
 
 
 VAL_SEED = 7_000_003      # synthetic validation batches: the same draws at every pass, so the series is comparable over a run
+VIS_SEED = 7_100_019      # the synthetic test-visualisation batch
+LOSS_TAGS = (("Loss/G", "loss_G"), ("Loss/G/l1_cloth", "l1"), ("Loss/G/vgg", "vgg"), ("Loss/G/tv", "tv"), ("Loss/G/CE", "ce"),
+             ("Loss/G/GAN", "g_gan"), ("Loss/D", "loss_D"), ("Loss/D/pred_real", "d_real"), ("Loss/D/pred_fake", "d_fake"))
 
 
 class _Validation(object):
@@ -150,7 +170,8 @@ class _Validation(object):
     def __init__(self, opt, device):
         self.opt, self.device = opt, device
         self.loader = None
-        self.board = ScalarLog(os.path.join(opt.tensorboard_dir, opt.name))
+        self.board = viz.BoardLog(os.path.join(opt.tensorboard_dir, opt.name))
+        self.vis = None
 
     def batches(self):
         opt = self.opt
@@ -169,6 +190,34 @@ class _Validation(object):
             self.board.add_scalar("val/iou", res["iou"], step + 1)
             print("step: %8d, val/iou: %.6f (%d items)" % (step + 1, res["iou"], res["items"]), flush=True)
         return res
+
+    def vis_batch(self):
+        """The test-visualisation batch (:384-399): the first --num_test_visualize test items, loaded once."""
+        if self.vis is None:
+            opt, n = self.opt, self.opt.num_test_visualize
+            if opt.synthetic:
+                self.vis = synthetic_batch(opt, n, VIS_SEED, self.device)
+                self.vis["image"] = synthetic_image(opt, n, VIS_SEED, self.device)
+            else:
+                loader, _ = val_items_loader(opt, n, n)
+                raw = next(iter(loader))
+                self.vis = disk_batch(raw, self.device, opt.test_datasetting)
+                self.vis["image"] = raw["image"].to(self.device)
+        return self.vis
+
+    def record(self, tocg, step, losses, batch, aux):
+        """train_condition.py:362-436: the loss scalars, ``train_images`` (sample 0 of the training batch) and ``test_images/{i}``."""
+        opt, s = self.opt, step + 1
+        for tag, key in LOSS_TAGS:
+            if key in losses and not (key == "vgg" and opt.no_vgg_loss):
+                v = losses[key]
+                self.board.add_scalar(tag, float(v.detach()) if torch.is_tensor(v) else float(v), s)
+        self.board.add_image("train_images", viz.condition_grid(batch, aux, quant=viz.TRUNC, count=1)[0], s)
+        if not opt.no_test_visualize and opt.num_test_visualize > 0:
+            vb = self.vis_batch()
+            grids = viz.to_host(viz.condition_grid(vb, viz.condition_fields(opt, tocg, vb), quant=viz.TRUNC))
+            for i in range(grids.shape[0]):
+                self.board.add_image("test_images/%d" % i, grids[i], s)
 
 
 def main(argv=None):
@@ -226,13 +275,22 @@ def main(argv=None):
     validation = _Validation(opt, dev) if rank == 0 else None
     for step in range(opt.load_step, last):
         t0 = time.time()
+        record = opt.board and validation is not None and validation_due(step, opt.tensorboard_count)       # :362
         if loader is None:
             batch = synthetic_batch(opt, per_rank, hdist.shard_seed(4321 + step * 89, rank), dev)
+            if record:
+                batch["image"] = synthetic_image(opt, per_rank, hdist.shard_seed(4321 + step * 89, rank), dev)
         else:
-            batch = disk_batch(loader.next_batch(), dev)
-        losses = condition_train_step(opt, tocg, D, crit_l1, crit_vgg, crit_gan, opt_g, opt_d, batch, sync_g, sync_d)
+            raw = loader.next_batch()
+            batch = disk_batch(raw, dev)
+            if record:
+                batch["image"] = raw["image"].to(dev)
+        aux = {} if record else None
+        losses = condition_train_step(opt, tocg, D, crit_l1, crit_vgg, crit_gan, opt_g, opt_d, batch, sync_g, sync_d, aux=aux)
         if validation_due(step, opt.val_count) and validation is not None:          # :313-360
             validation.run(tocg, step)
+        if record:
+            validation.record(tocg, step, losses, batch, aux)
         if (step + 1) % opt.display_count == 0 and rank == 0:
             torch.cuda.synchronize()
             t = time.time() - t0

@@ -16,8 +16,14 @@ on the MI355X-native hot path.
     batches under ``--synthetic``), batch ``--val_batch_size``, and logs ``test/LPIPS`` of the 128x128 resizes to
     ``<tensorboard_dir>/<name>/scalars.jsonl`` (and to tensorboard where a SummaryWriter is importable): hr_viton_amd.validate,
     which states the deviations.  The LPIPS weights are read from ``--lpips_weights`` / ``--alexnet_weights`` and never downloaded;
-    where they are missing the pass is skipped with one note.  The tensorboard loss scalars and image grids (``make_image_grid``,
-    :364-478) are out of scope.
+    where they are missing the pass is skipped with one note.
+  * recording (train_generator.py:364-478) is opt-in: with ``--board`` rank 0 records, every ``--tensorboard_count`` steps, the loss
+    scalars under the reference's tags (``Loss/gen``, ``Loss/gen/adv``, ``Loss/gen/feat``, ``Loss/gen/vgg``, ``Loss/dis``,
+    ``Loss/dis/adv_fake``, ``Loss/dis/adv_real``; a term that is switched off is skipped) into ``scalars.jsonl``, and the 10-panel
+    grids (the reference's ``make_image_grid``) ``train_images`` and ``test_images/{i}``, i < ``--num_test_visualize`` (frozen
+    pipeline + generator in eval mode on test items) as PNGs under ``<tensorboard_dir>/<name>/images/``, composed and quantised in one
+    HIP launch (hr_viton_amd.viz, which states the deviations).  Without ``--board`` nothing of this is computed or written and
+    ``--tensorboard_count`` is ignored.
 Bug-fixes of the reference call sites: tocg(input1, input2) arity, load_checkpoint arity,
 Adam betas as floats.
 """
@@ -35,6 +41,7 @@ if ROOT not in sys.path:
 
 import hr_viton_amd  # noqa: E402,F401
 from hr_viton_amd import dist as hdist  # noqa: E402
+from hr_viton_amd import viz  # noqa: E402
 from hr_viton_amd.checkpoint import load_checkpoint, save_checkpoint  # noqa: E402
 from hr_viton_amd.gen_train import attach_grad_sync  # noqa: E402
 from hr_viton_amd.losses import GANLoss, L1Loss  # noqa: E402
@@ -43,7 +50,7 @@ from hr_viton_amd.networks import ConditionGenerator  # noqa: E402
 from hr_viton_amd.optim import Adam  # noqa: E402
 from hr_viton_amd.parallel import broadcast_module  # noqa: E402
 from hr_viton_amd.pipeline import generator_train_step, make_generator_inputs  # noqa: E402
-from hr_viton_amd.validate import (ScalarLog, generator_validation_lpips, load_validation_lpips, val_items_loader,  # noqa: E402
+from hr_viton_amd.validate import (generator_validation_lpips, load_validation_lpips, val_items_loader,  # noqa: E402
                                    validation_due)
 from hr_viton_amd.vgg import VGGLoss  # noqa: E402
 
@@ -120,6 +127,8 @@ def get_opt(argv=None):
                    help="plumbing only: test/LPIPS on randomly initialised AlexNet / lin weights (labelled); implied by --synthetic")
     p.add_argument("--val_items", type=int, default=500, help="test items scored per test/LPIPS pass (the reference's 500)")
     p.add_argument("--val_batch_size", type=int, default=1, help="batch of the test/LPIPS pass (the reference's 1)")
+    p.add_argument("--board", action="store_true",
+                   help="every --tensorboard_count steps record the loss scalars and the image grids (train_generator.py:364-478)")
     opt = p.parse_args(argv)
     opt.gpu_ids = [int(s) for s in str(opt.gpu_ids).split(",") if s.strip() and int(s) >= 0]
     return opt
@@ -137,11 +146,12 @@ def synthetic_batch(opt, n, seed, device):
 
 
 VAL_SEED = 9_000_011      # synthetic validation batches: the same draws at every pass, so the series is comparable over a run
+VIS_SEED = 9_100_003      # the synthetic test-visualisation batch
 
 
-def disk_batch(raw, dev):
+def disk_batch(raw, dev, datasetting="paired"):
     """cp_dataset.py batch -> the flat dictionary make_generator_inputs takes (train_generator.py:194-212)."""
-    return {"cloth": raw["cloth"]["paired"].to(dev), "cloth_mask": raw["cloth_mask"]["paired"].to(dev),
+    return {"cloth": raw["cloth"][datasetting].to(dev), "cloth_mask": raw["cloth_mask"][datasetting].to(dev),
             "parse_agnostic": raw["parse_agnostic"].to(dev), "densepose": raw["densepose"].to(dev),
             "agnostic": raw["agnostic"].to(dev), "image": raw["image"].to(dev),
             "parse": raw["parse"].to(dev), "parse_cloth": raw["parse_cloth"].to(dev)}
@@ -153,7 +163,40 @@ class _Validation(object):
     def __init__(self, opt, device):
         self.opt, self.device = opt, device
         self.loader, self.model, self.tried = None, None, False
-        self.board = ScalarLog(os.path.join(opt.tensorboard_dir, opt.name))
+        self.board = viz.BoardLog(os.path.join(opt.tensorboard_dir, opt.name))
+        self.vis = None
+
+    def vis_batch(self):
+        """The test-visualisation batch (:383-395): the first --num_test_visualize test items with the unpaired cloth, loaded once."""
+        if self.vis is None:
+            opt, n = self.opt, self.opt.num_test_visualize
+            if opt.synthetic:
+                self.vis = synthetic_batch(opt, n, VIS_SEED, self.device)
+            else:
+                loader, _ = val_items_loader(opt, n, n)
+                self.vis = disk_batch(next(iter(loader)), self.device, "unpaired")
+        return self.vis
+
+    def record(self, tocg, generator, step, losses, batch, aux, output):
+        """train_generator.py:364-478: ``train_images`` (sample 0 of the training batch), the loss scalars and ``test_images/{i}``."""
+        opt, s = self.opt, step + 1
+        self.board.add_image("train_images", viz.generator_train_grid(batch, aux, output, quant=viz.TRUNC, count=1)[0], s)
+        losses = {k: v.detach() for k, v in losses.items()}
+        gen = [v for k, v in losses.items() if not k.startswith("D_")]
+        dis = [v for k, v in losses.items() if k.startswith("D_")]
+        self.board.add_scalar("Loss/gen", float(sum(gen).mean()), s)
+        for tag, key in (("Loss/gen/adv", "GAN"), ("Loss/gen/feat", "GAN_Feat"), ("Loss/gen/vgg", "VGG")):
+            if key in losses:
+                self.board.add_scalar(tag, float(losses[key].mean()), s)
+        self.board.add_scalar("Loss/dis", float(sum(dis).mean()), s)
+        self.board.add_scalar("Loss/dis/adv_fake", float(losses["D_Fake"].mean()), s)
+        self.board.add_scalar("Loss/dis/adv_real", float(losses["D_Real"].mean()), s)
+        if opt.num_test_visualize > 0:
+            vb = self.vis_batch()
+            fields, out = viz.generator_fields(opt, tocg, generator, vb)
+            grids = viz.to_host(viz.generator_train_grid(vb, fields, out, quant=viz.TRUNC))
+            for i in range(grids.shape[0]):
+                self.board.add_image("test_images/%d" % i, grids[i], s)
 
     def batches(self):
         opt, bs = self.opt, max(1, self.opt.val_batch_size)
@@ -262,9 +305,13 @@ def main(argv=None):
             batch = synthetic_batch(opt, per_rank, hdist.shard_seed(1234 + step * 97, rank), dev)
         else:
             batch = disk_batch(loader.next_batch(), dev)               # train_generator.py:194-212
-        x, parse7 = make_generator_inputs(opt, tocg, batch)
+        record = opt.board and validation is not None and validation_due(step, opt.tensorboard_count)       # :364
+        aux = {} if record else None
+        x, parse7 = make_generator_inputs(opt, tocg, batch, aux=aux)
         losses, _ = generator_train_step(opt, generator, discriminator, crit_gan, crit_feat, crit_vgg, opt_g, opt_d, x,
-                                         parse7, batch["image"], sync_g, sync_d)
+                                         parse7, batch["image"], sync_g, sync_d, aux=aux)
+        if record:
+            validation.record(tocg, generator, step, losses, batch, aux, aux["output"])
         if validation_due(step, opt.lpips_count) and validation is not None:        # :480-584
             validation.run(tocg, generator, step)
         if (step + 1) % opt.display_count == 0 and rank == 0:
