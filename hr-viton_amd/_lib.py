@@ -91,7 +91,8 @@ class hrv_spade_fused_t(C.Structure):
                 ("act", C.c_int32), ("act_slope", C.c_float),
                 ("out", C.c_void_p), ("out_cstride", C.c_int32), ("out_coff", C.c_int32),
                 ("actv", C.c_void_p), ("actv_cstride", C.c_int32), ("actv_coff", C.c_int32),
-                ("x_up_channels", C.c_int32), ("x2", C.c_void_p), ("x2_cstride", C.c_int32), ("x2_coff", C.c_int32)]
+                ("x_up_channels", C.c_int32), ("x2", C.c_void_p), ("x2_cstride", C.c_int32), ("x2_coff", C.c_int32),
+                ("tiles", C.c_void_p), ("gb_table", C.c_void_p), ("tiles_phase", C.c_int32)]
 
 
 class hrv_conv_p2_t(C.Structure):
@@ -330,6 +331,8 @@ SYMBOLS = {
     "hrv_spade_fused_supported": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "hrv_spade_fused_pack_dev": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp]),
     "hrv_spade_fused_bf16": (C.c_int, [C.POINTER(hrv_spade_fused_t), _vp]),
+    "hrv_spade_tiles_plan_bytes": (C.c_int64, [_i32, _i32, _i32]),
+    "hrv_spade_tiles_bf16": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "hrv_tv_loss_f32": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "hrv_rgb_to_gray_u8": (C.c_int, [_vp, _i64, _vp, _vp]),
     "hrv_pair_stats_workspace_bytes": (_i64, [_i32, _i32, _i32]),

@@ -39,6 +39,17 @@ __device__ __forceinline__ PatchTile patch_tile(const int bid, const int W, cons
   return t;
 }
 
+// tile number `mt` (no remap: the caller read it from a list) -> image, top-left corner
+__device__ __forceinline__ PatchTile patch_tile_at(const int mt, const int W, const int H) {
+  const int tx = (W + 15) >> 4, ty = (H + 15) >> 4;
+  PatchTile t;
+  t.n = mt / (tx * ty);
+  const int rr = mt - t.n * (tx * ty);
+  t.y0 = (rr / tx) << 4;
+  t.x0 = (rr % tx) << 4;
+  return t;
+}
+
 // registers 4g .. 4g+3 of an accumulator tile (swapped operands: 4 consecutive columns of the lane's pixel)
 __device__ __forceinline__ f32x4 acc4(const f32x16& a, int g) {
   f32x4 r;

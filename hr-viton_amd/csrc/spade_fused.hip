@@ -34,6 +34,7 @@
 #include <utility>
 
 #include "patch_pass.h"
+#include "spade_tiles.h"
 
 namespace hrv {
 
@@ -73,7 +74,24 @@ struct GfParams {
   void* actv; int actv_cs, actv_co;        // optional: ReLU(conv_shared(seg)) as bf16 NHWC (training forward, for the backward)
   unsigned long long* tlog;
   int pp;                   // one (tile, pass) per unit of work (see spade_fused_kernel)
+  // the tile plan (spade_tiles.h; null: every tile does the matrix work): the kernel works through the plan's HEAVY list, and a
+  // flagged representative tile also leaves its gamma|beta accumulators in row k of gtab = fp32 [8][2][sC] (gamma | beta) for
+  // spade_uniform_kernel, which serves the light list from it
+  const int* tplan;
+  float* gtab;
 };
+
+// unit `bid` of a launch over `nt` tiles: the tile itself, or entry `bid` of the plan's heavy list
+// (the plan does not change while this kernel runs, but the kernel stores to global memory, so a plain load of it is a VECTOR load
+//  whose result -- tile corner, unit count -- drags the scheduler's scalar arithmetic into vector registers: read it through the
+//  constant address space, i.e. with scalar loads)
+typedef const __attribute__((address_space(4))) int* gf_cint_p;
+__device__ __forceinline__ int gf_plan_word(const GfParams& p, const int i) { return ((gf_cint_p)p.tplan)[i]; }
+__device__ __forceinline__ int gf_heavy_entry(const GfParams& p, const int bid, const int nt) { return gf_plan_word(p, ST_HDR + xcd_remap(bid, nt)); }
+__device__ __forceinline__ PatchTile gf_tile(const GfParams& p, const int bid, const int nt) {
+  if (!p.tplan) return patch_tile(bid, p.W, p.H, p.m_tiles);
+  return patch_tile_at(gf_heavy_entry(p, bid, nt) & ST_TILE_MASK, p.W, p.H);
+}
 
 // columns = (gamma32 | beta32) pairs (+ one 16|16 tail tile) of C norm channels; passes of 4 column tiles, then one of 2,
 // then (16-channel tail) one of 5 = two pairs + the tail
@@ -629,6 +647,8 @@ __device__ __forceinline__ void gf_pass(const GfParams& p, unsigned char* const 
       }
     }
   };
+  // (the plan entry is read again here, not carried through the main loop)
+  const int rep_k = p.tplan ? gf_heavy_entry(p, bid, gf_plan_word(p, ST_NHEAVY)) >> 24 : 0;
   float zv[2] = {0.f, 0.f};
   if (p.sz) {
 #pragma unroll
@@ -690,6 +710,17 @@ __device__ __forceinline__ void gf_pass(const GfParams& p, unsigned char* const 
       }
     }
     const int cb = cb0 + lc0;                // first norm channel of the group
+    if (rep_k > 0) {
+      // a representative tile (wave-uniform branch; every pixel of the tile holds these bits): pixel 0 of wave 0 -> the table
+      const rsrc_t t_rsrc = make_rsrc(p.gtab + (size_t)(rep_k - 1) * 2 * p.sC, (unsigned)(2 * p.sC * 4));
+      const bool mine = wave == 0 && l31e == 0;
+#pragma unroll
+      for (int g = 0; g < NG; ++g) {
+        const unsigned c4 = (unsigned)(cb + 8 * g + 4 * lhe) * 4u;
+        store16(gam(0, g), t_rsrc, mine ? c4 : 0xFFFFFFF0u);
+        store16(bet(0, g), t_rsrc, mine ? c4 + (unsigned)p.sC * 4u : 0xFFFFFFF0u);
+      }
+    }
     // same wave wrote and reads: LDS operations of a wave complete in order
     rows_out(ng_c, o_rsrc, p.out_cs, p.out_co + cb);
     if (p.g1p) {
@@ -732,7 +763,9 @@ __global__ __launch_bounds__(256, 2) void spade_fused_kernel(const GfParams p, c
         reinterpret_cast<const float*>(reinterpret_cast<const char*>(p.wp) + GF_WSH_B)[threadIdx.x];
   // (a tile's passes share its label patch: loaded with the first, `nxt_seg`; p.pp: the 128 x 96 / 64 x 48 levels)
   int c_n = -1;                                // image of the constants in LDS (the scheduler keys them on the pass)
-#define GF_TILE(BID) patch_tile(BID, p.W, p.H, p.m_tiles)
+  // the units of work: the plan's heavy tiles (device-side count; grid and pp are the host's, from the total)
+  struct { int pp, m_tiles; } sch = {p.pp, p.tplan ? gf_plan_word(p, ST_NHEAVY) : p.m_tiles};
+#define GF_TILE(BID) gf_tile(p, BID, sch.m_tiles)
 #define GF_HEAD(PASS, T) gf_head<NTP>(p, PASS, smem, T, true, wave, lane)
 #define GF_PASS(PASS, T, BID, STALE, BLOCK_FIRST, FIRST, LAST, NXT_PASS, NT_)                                            \
   {                                                                                                                     \
@@ -740,10 +773,97 @@ __global__ __launch_bounds__(256, 2) void spade_fused_kernel(const GfParams p, c
     c_n = T.n;                                                                                                          \
     gf_pass<NTP>(p, smem, PASS, T, BID, lc, BLOCK_FIRST, p.actv != nullptr && PASS == 0, FIRST, LAST, NXT_PASS, NT_, LAST); \
   }
-  PATCH_PASS_UNITS(p, pass0, pass1, GF_TILE, GF_HEAD, GF_PASS, p.tlog)
+  PATCH_PASS_UNITS(sch, pass0, pass1, GF_TILE, GF_HEAD, GF_PASS, p.tlog)
 #undef GF_TILE
 #undef GF_HEAD
 #undef GF_PASS
+}
+
+// ------------------------------------------------------------------------------------------------ the light tiles
+// The epilogue of gf_pass alone, over the plan's LIGHT list: gamma|beta of such a tile are row k of the table its class's
+// representative left (spade_fused_kernel ran first, on the same stream), its actv is the representative's row.  HBM-bound: x
+// in, out (and 1 + gamma, actv) out.  Bit-identical to what spade_fused_kernel writes for the tile: the same operations in the
+// same order, contraction spelled out (the fused epilogue contracts x * rstd + (...) and xn * g1 + (...) into FMAs).
+constexpr int GU_MAXC = 1024;
+#pragma clang fp contract(off)
+__global__ __launch_bounds__(256) void spade_uniform_kernel(const GfParams p) {
+  __shared__ float cv[5][GU_MAXC];             // per channel: 1 + gamma' | beta' | rstd | noise_scale * rstd | -mean * rstd
+  const int nl = p.tplan[ST_NLIGHT];
+  const int* const light = p.tplan + ST_HDR + p.m_tiles;
+  const int tid = threadIdx.x;
+  const int C = p.sC, CG = C >> 3;
+  const float sl = p.act == HRV_ACT_LRELU ? p.slope : (p.act == HRV_ACT_RELU ? 0.f : 1.f);
+  for (int u = blockIdx.x; u < nl; u += gridDim.x) {
+    const int ent = light[u];
+    const int k = ent >> 24;
+    const PatchTile T = patch_tile_at(ent & ST_TILE_MASK, p.W, p.H);
+    __syncthreads();
+    for (int c = tid; c < C; c += 256) {
+      const float b1 = 1.f + p.bg[c];
+      const float b2 = p.bb[c];
+      const float rs = p.srstd[(size_t)T.n * C + c];
+      const float nr = p.sns ? p.sns[c] * rs : 0.f;
+      const float mr = -p.smean[(size_t)T.n * C + c] * rs;
+      cv[0][c] = p.gtab[(size_t)(2 * k) * C + c] + b1;
+      cv[1][c] = p.gtab[(size_t)(2 * k + 1) * C + c] + b2;
+      cv[2][c] = rs; cv[3][c] = nr; cv[4][c] = mr;
+    }
+    __syncthreads();
+    for (int idx = tid; idx < 256 * CG; idx += 256) {
+      const int pix = idx / CG, c0 = (idx - pix * CG) << 3;
+      const int y = T.y0 + (pix >> 4), x = T.x0 + (pix & 15);
+      const size_t pidx = ((size_t)T.n * p.H + y) * p.W + x;
+      f32x4 xr[2];
+      if (p.sx_up_c > 0) {
+        const bool lo = c0 < p.sx_up_c;
+        const size_t plo = ((size_t)T.n * (p.H >> 1) + (y >> 1)) * (p.W >> 1) + (x >> 1);
+        const float* const src = lo ? p.sx + plo * p.sx_cs + p.sx_co + c0 : p.sx2 + pidx * p.sx2_cs + p.sx2_co + c0 - p.sx_up_c;
+        xr[0] = ld4e<false>(src, 0); xr[1] = ld4e<false>(src, 4);
+      } else if (p.sx_f32) {
+        xr[0] = ld4e<false>(p.sx, pidx * p.sx_cs + p.sx_co + c0); xr[1] = ld4e<false>(p.sx, pidx * p.sx_cs + p.sx_co + c0 + 4);
+      } else {
+        xr[0] = ld4e<true>(p.sx, pidx * p.sx_cs + p.sx_co + c0); xr[1] = ld4e<true>(p.sx, pidx * p.sx_cs + p.sx_co + c0 + 4);
+      }
+      const float zv = p.sz ? p.sz[((size_t)T.n * p.W + x) * p.H + y] : 0.f;
+      gf_bf16x4 ov[2], gv[2];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        f32x4 g1, v;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int c = c0 + 4 * h + e;
+          const float xn = __builtin_fmaf(xr[h][e], cv[2][c], __builtin_fmaf(cv[3][c], zv, cv[4][c]));
+          g1[e] = cv[0][c];
+          const float t = __builtin_fmaf(xn, g1[e], cv[1][c]);
+          const float ts = t * sl;
+          v[e] = fmaxf(t, ts);
+        }
+        ov[h] = __builtin_convertvector(v, gf_bf16x4);
+        gv[h] = __builtin_convertvector(g1, gf_bf16x4);
+      }
+      unsigned short* const o = reinterpret_cast<unsigned short*>(p.out) + pidx * p.out_cs + p.out_co + c0;
+      *reinterpret_cast<gf_bf16x4*>(o) = ov[0];
+      *reinterpret_cast<gf_bf16x4*>(o + 4) = ov[1];
+      if (p.g1p) {
+        unsigned short* const g = reinterpret_cast<unsigned short*>(p.g1p) + pidx * C + c0;
+        *reinterpret_cast<gf_bf16x4*>(g) = gv[0];
+        *reinterpret_cast<gf_bf16x4*>(g + 4) = gv[1];
+      }
+    }
+    if (p.actv) {
+      // the class's actv row: every pixel of the representative tile holds it (that tile is heavy: nobody writes it here)
+      const PatchTile R = patch_tile_at(p.tplan[ST_REP + k], p.W, p.H);
+      unsigned short* const a = reinterpret_cast<unsigned short*>(p.actv);
+      const int g = tid & 15;
+      const uint4 row = *reinterpret_cast<const uint4*>(a + (((size_t)R.n * p.H + R.y0) * p.W + R.x0) * p.actv_cs + p.actv_co + 8 * g);
+#pragma unroll 4
+      for (int i = 0; i < 16; ++i) {
+        const int pix = (tid >> 4) + 16 * i;
+        const size_t pidx = ((size_t)T.n * p.H + T.y0 + (pix >> 4)) * p.W + T.x0 + (pix & 15);
+        *reinterpret_cast<uint4*>(a + pidx * p.actv_cs + p.actv_co + 8 * g) = row;
+      }
+    }
+  }
 }
 
 }  // namespace hrv
@@ -805,6 +925,9 @@ extern "C" int hrv_spade_fused_bf16(const hrv_spade_fused_t* d, hrv_stream_t str
   HRV_REQUIRE(d->actv == nullptr || (d->actv_cstride % 8 == 0 && d->actv_coff % 8 == 0 && d->actv_coff + 128 <= d->actv_cstride &&
                                      (int64_t)d->H * d->W * d->actv_cstride * 2 < (int64_t)0xFFFFFFF0),
               "spade_fused: actv slice");
+  HRV_REQUIRE(d->tiles == nullptr || (d->gb_table != nullptr && (((uintptr_t)d->tiles & 3) == 0) && (((uintptr_t)d->gb_table & 15) == 0) &&
+                                      d->C <= GU_MAXC && patch_tiles(d->N, d->H, d->W) < ST_MAX_TILES && d->tiles_phase >= 0 && d->tiles_phase <= 2),
+              "spade_fused: tile plan (gb_table [8][2][C] fp32 goes with it, C <= %d, tiles_phase 0..2)", GU_MAXC);
   GfParams p;
   memset(&p, 0, sizeof(p));
   p.seg = d->seg; p.seg_H = d->seg_H; p.seg_W = d->seg_W; p.seg_shift = d->seg_shift; p.seg_bytes = (unsigned)sbytes;
@@ -822,11 +945,19 @@ extern "C" int hrv_spade_fused_bf16(const hrv_spade_fused_t* d, hrv_stream_t str
   p.tlog = diag_tlog(p.m_tiles);
   p.pp = patch_pp(p.m_tiles) ? 1 : 0;
   if (p.pp) p.tlog = nullptr;          // (the timeline's slots are per tile)
+  p.tplan = (const int*)d->tiles; p.gtab = d->gb_table;
+  // tiles_phase: 0 = both kernels (production), 1 = the heavy list only, 2 = the light list only (the profiler times them apart)
+  const bool run_heavy = !p.tplan || d->tiles_phase != 2, run_light = p.tplan && d->tiles_phase != 1;
   // 4-tile passes, a 2-tile pass, the 5-tile tail pass
-  patch_pass_groups(pl, p.m_tiles, p.pp != 0, [](int) { return 2; }, [&](const int a, const int b, const int grid) {
+  if (run_heavy) patch_pass_groups(pl, p.m_tiles, p.pp != 0, [](int) { return 2; }, [&](const int a, const int b, const int grid) {
     if (pl.ntp[a] == 4) hipLaunchKernelGGL((spade_fused_kernel<4>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p, a, b);
     else if (pl.ntp[a] == 2) hipLaunchKernelGGL((spade_fused_kernel<2>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p, a, b);
     else hipLaunchKernelGGL((spade_fused_kernel<5>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p, a, b);
   });
+  if (run_light) {
+    // (the light count lives on the device: a fixed grid strides over the list; a count of 0 is a no-op)
+    const int cap = 4 * persistent_cus();
+    hipLaunchKernelGGL(spade_uniform_kernel, dim3(p.m_tiles < cap ? p.m_tiles : cap), dim3(256), 0, (hipStream_t)stream, p);
+  }
   return check_launch("spade_fused_kernel");
 }

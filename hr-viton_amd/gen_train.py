@@ -284,7 +284,8 @@ class SpadeT:
             g1p = torch.empty((x.N, x.H, x.W, self.Cp), dtype=torch.bfloat16, device=dev) if save else None
             pk = T.spade_fused_pack(self.shared.wparam.data, self.shared.bparam.data, n.conv_gamma.weight.data, n.conv_beta.weight.data)
             T.spade_fused_forward(sg, shift, x, mean, rstd, zz, n.noise_scale.data, pk, n.conv_gamma.bias.data, n.conv_beta.bias.data,
-                                  self.act, 0.2, out, g1p, actv if save else None, self.name + ".conv_shared+gamma|beta")
+                                  self.act, 0.2, out, g1p, actv if save else None, self.name + ".conv_shared+gamma|beta",
+                                  tiles=T.spade_tile_plan_for(sg, shift, x.N, x.H, x.W))
             ctx = dict(x=x, z=zz, ns=ns, mean=mean, rstd=rstd, actv=actv, g1p=Act(g1p, self.C) if save else None, out=out)
             return out, ctx
         # bias of the fused conv in its interleaved (gamma32 | beta32) column order + padded noise scale: one launch

@@ -188,7 +188,8 @@ class _SpadePlan:
             pk, bg, bb = self._gf
             out = ops.alloc(x.N, x.H, x.W, self.mod.Creal, dev, bf16=True)
             T.spade_fused_forward(seg, shift, x, mean, rstd, zz, self.mod.ns if zz is not None else None, pk, bg, bb, self.mod.conv.act,
-                                  self.mod.conv.slope, out, None, None, self.mod.conv.name.replace("conv_gamma|beta", "conv_shared+gamma|beta"))
+                                  self.mod.conv.slope, out, None, None, self.mod.conv.name.replace("conv_gamma|beta", "conv_shared+gamma|beta"),
+                                  tiles=T.spade_tile_plan_for(seg, shift, x.N, x.H, x.W))
             return out
         return self.mod(actv, x, mean, rstd, zz)
 

@@ -1286,12 +1286,76 @@ def spade_fused_pack(w_shared: torch.Tensor, b_shared: torch.Tensor, w_gamma: to
     return buf
 
 
+class SpadeTilePlan:
+    """Which 16x16-pixel tiles of a label map at one level carry ONE one-hot label over their whole 20x20 patch (light: gamma|beta
+    are a constant there, the fused forward gives them the epilogue alone) and which need the matrix work (heavy).  Device side
+    (csrc/spade_tiles.hip; layout in csrc/spade_tiles.h): nothing here reads it back unless asked (``counts``)."""
+    HDR = 16
+
+    def __init__(self, ws: torch.Tensor, N: int, H: int, W: int, seg_shift: int):
+        self.ws, self.N, self.H, self.W, self.seg_shift = ws, N, H, W, seg_shift
+        self.tiles = N * ((H + 15) // 16) * ((W + 15) // 16)
+        self._counts = None
+
+    def counts(self) -> Tuple[int, int]:
+        """(heavy, light) -- a host read-back: diagnostics, tests and the profiler's accounting only"""
+        if self._counts is None:
+            h, l = self.ws[:2].tolist()
+            self._counts = (int(h), int(l))
+        return self._counts
+
+    def lists(self):
+        """(heavy entries, light entries, representatives[8]) as Python lists (read-back: tests, tools)"""
+        w = self.ws.tolist()
+        nh, nl, m = w[0], w[1], self.tiles
+        return w[self.HDR:self.HDR + nh], w[self.HDR + m:self.HDR + m + nl], w[2:10]
+
+
+def spade_tile_plan(seg: Act, seg_shift: int, N: int, H: int, W: int) -> SpadeTilePlan:
+    """Classify the tiles of the (N, H, W) level that reads the bf16 label map ``seg`` at (y << seg_shift, x << seg_shift)."""
+    lib = _lib.load()
+    ops.require_cuda(seg.t, "spade_tile_plan")
+    assert seg.bf16 and seg.cstride == 8 and seg.coff == 0 and seg.t.is_contiguous()
+    nbytes = lib.hrv_spade_tiles_plan_bytes(N, H, W)
+    assert nbytes > 0, (N, H, W)
+    ws = torch.empty(nbytes // 4, dtype=torch.int32, device=seg.t.device)
+    with ops._Timed("glue", "spade tile plan %dx%d" % (H, W), 0.0, 16.0 * N * H * W):
+        _lib.check(lib.hrv_spade_tiles_bf16(seg.t.data_ptr(), seg.H, seg.W, seg_shift, N, H, W, ws.data_ptr(), _stream()), "hrv_spade_tiles_bf16")
+    return SpadeTilePlan(ws, N, H, W, seg_shift)
+
+
+def spade_uniform_min_tiles() -> int:
+    """Levels with fewer tiles than this keep every tile on the matrix path (HRV_SPADE_UNIFORM_MIN_TILES)."""
+    try:
+        return max(1, int(os.environ.get("HRV_SPADE_UNIFORM_MIN_TILES", "2048")))
+    except ValueError:
+        return 2048
+
+
+def spade_tile_plan_for(seg: Act, seg_shift: int, N: int, H: int, W: int) -> Optional[SpadeTilePlan]:
+    """The tile plan of this level, computed once per label map and level and kept ON the label-map Act (as its bf16 copy is:
+    shared by the three norms of a block and by both generator forwards of a step; a new label map is a new Act).  None: the
+    switch is off (HRV_SPADE_UNIFORM=0) or the level is below the tile threshold."""
+    if os.environ.get("HRV_SPADE_UNIFORM", "1") == "0":
+        return None
+    if N * ((H + 15) // 16) * ((W + 15) // 16) < spade_uniform_min_tiles():
+        return None
+    cache = seg.__dict__.setdefault("_tile_plans", {})
+    key = (seg_shift, N, H, W, seg.t.data_ptr(), seg.t._version)
+    plan = cache.get(key)
+    if plan is None:
+        plan = cache[key] = spade_tile_plan(seg, seg_shift, N, H, W)
+    return plan
+
+
 def spade_fused_forward(seg: Act, seg_shift: int, x: Act, mean: torch.Tensor, rstd: torch.Tensor, z: Optional[torch.Tensor],
                         noise_scale: Optional[torch.Tensor], packed: torch.Tensor, bias_gamma: torch.Tensor, bias_beta: torch.Tensor,
-                        act: int, slope: float, out: Act, g1p: Optional[torch.Tensor], actv: Optional[Act], name: str):
+                        act: int, slope: float, out: Act, g1p: Optional[torch.Tensor], actv: Optional[Act], name: str,
+                        tiles: Optional[SpadeTilePlan] = None):
     """out = act(IN(x + z*noise_scale) * (1 + conv_gamma(a)) + conv_beta(a)), a = ReLU(conv_shared(nearest(seg))) computed in the
     kernel; g1p (optional) <- 1 + gamma; actv (optional, bf16 slice of 128 channels) <- a.  ``seg``: the bf16 label map
-    [N, H << seg_shift, W << seg_shift, 8]."""
+    [N, H << seg_shift, W << seg_shift, 8].  ``tiles``: the label map's tile plan at this level (spade_tile_plan): the light tiles
+    skip the matrix work (same bits out); None: every tile takes it."""
     lib = _lib.load()
     assert seg.bf16 and seg.cstride == 8 and seg.coff == 0 and out.bf16
     d = _lib.hrv_spade_fused_t()
@@ -1322,6 +1386,23 @@ def spade_fused_forward(seg: Act, seg_shift: int, x: Act, mean: torch.Tensor, rs
     fl = 2.0 * px * 2 * C_ * 128 * 9          # the gamma|beta convolution (SURVEY 8d work; conv_shared's 2 * 72 * 128 per pixel rides along)
     nbytes = (px * 16 + xbytes + (px * 2.0 * C_ if g1p is not None else 0.0) + ops.act_bytes(out) + (px * 256 if actv is not None else 0.0) +
               2.0 * C_ * 128 * 9 * 2)
+    if tiles is not None:
+        assert (tiles.N, tiles.H, tiles.W, tiles.seg_shift) == (x.N, x.H, x.W, seg_shift), "tile plan of another level"
+        gtab = torch.empty(8 * 2 * C_, dtype=torch.float32, device=out.t.device)      # the representatives' gamma|beta, this launch's
+        d.tiles, d.gb_table = tiles.ws.data_ptr(), gtab.data_ptr()
+        if ops._Prof.enabled:
+            # the profiler's accounting (outside any timed region): the matrix kernel is credited with the tiles it executed (a
+            # read-back of the heavy count), the light tiles' kernel is a launch of its own, bytes only
+            heavy, light = tiles.counts()
+            fh, fl_ = heavy / float(tiles.tiles), light / float(tiles.tiles)
+            wbytes = 2.0 * C_ * 128 * 9 * 2
+            d.tiles_phase = 1
+            with ops._Timed("conv", name + " [spade_gb]", fl * fh, (nbytes - wbytes) * fh + wbytes, "spade_fused_kernel"):
+                _lib.check(lib.hrv_spade_fused_bf16(C.byref(d), _stream()), "hrv_spade_fused_bf16")
+            d.tiles_phase = 2
+            with ops._Timed("conv", name + " [uniform tiles]", 0.0, (nbytes - wbytes - px * 16) * fl_, "spade_uniform_kernel"):
+                _lib.check(lib.hrv_spade_fused_bf16(C.byref(d), _stream()), "hrv_spade_fused_bf16[uniform]")
+            return
     with ops._Timed("conv", name + " [spade_gb]", fl, nbytes, "spade_fused_kernel"):      # (the tag: bench.py prices this kernel family's launches)
         _lib.check(lib.hrv_spade_fused_bf16(C.byref(d), _stream()), "hrv_spade_fused_bf16")
 

@@ -796,6 +796,12 @@ typedef struct hrv_spade_fused {
    * from `x` = lo [N][H/2][W/2][x_cstride] at (y >> 1, x >> 1), the rest from `x2` = hi [N][H][W][x2_cstride] (see hrv_norm_bwd_t) */
   int32_t x_up_channels;
   const void* x2; int32_t x2_cstride, x2_coff;
+  /* optional tile plan (hrv_spade_tiles_bf16 of the same label map, shift and extent; NULL: every tile does the matrix work):
+   * spade_fused_kernel works through the plan's heavy tiles, spade_uniform_kernel (same call, same stream, right behind it) gives
+   * the light ones -- one one-hot label over the whole 20x20 patch, gamma|beta a constant -- the epilogue alone, bit-identical.
+   * gb_table: fp32 [8][2][C] scratch of this launch (the representatives' gamma|beta).  tiles_phase: 0 both kernels, 1 / 2 only
+   * the heavy / the light part (two calls, 1 then 2, are one call with 0: a profiler times the kernels apart). */
+  const int32_t* tiles; float* gb_table; int32_t tiles_phase;
 } hrv_spade_fused_t;
 int64_t hrv_spade_fused_packed_bytes(int32_t C);   /* -1: norm width not served */
 int hrv_spade_fused_supported(int32_t C, int32_t hid, int32_t label_nc, int32_t N, int32_t H, int32_t W);
@@ -804,6 +810,14 @@ int hrv_spade_fused_supported(int32_t C, int32_t hid, int32_t label_nc, int32_t 
 int hrv_spade_fused_pack_dev(const float* w_shared, const float* b_shared, int32_t label_nc, const float* w_gamma,
                              const float* w_beta, int32_t C, void* out, hrv_stream_t stream);
 int hrv_spade_fused_bf16(const hrv_spade_fused_t* d, hrv_stream_t stream);
+/* The tile plan of a label map at one level (csrc/spade_tiles.h has the layout: int32 counts [0] heavy, [1] light, [2..9] the
+ * representative tile of each class or -1, from word 16 the heavy list, then the light list, patch_tiles(N, H, W) words each).
+ * A 16x16-pixel tile is LIGHT with class k when its 20x20 patch of sampled label pixels (y << seg_shift, x << seg_shift) lies wholly
+ * inside the H x W level image, all 400 16-byte vectors are bitwise equal and that vector is channel k = bf16 1.0, every other
+ * channel 0; every other tile is heavy, and so is the lowest light tile of each class (its representative).  Lists ascend. */
+int64_t hrv_spade_tiles_plan_bytes(int32_t N, int32_t H, int32_t W);   /* -1: extent not served */
+int hrv_spade_tiles_bf16(const void* seg, int32_t seg_H, int32_t seg_W, int32_t seg_shift, int32_t N, int32_t H, int32_t W,
+                         void* plan, hrv_stream_t stream);
 
 /* 3x3 stride-1 'same' convolution over ONE bf16-stored NHWC source, any Cin / Cout (the source keeps its channels padded to 8 with
  * zeros, `out` / `mask` / `residual` theirs padded to 16 bytes: the pad lanes of `out` receive zeros), two blocks per CU
