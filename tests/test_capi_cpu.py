@@ -263,3 +263,63 @@ def test_conv_s2_host_logic(lib):
     assert route(128, 64, 64, 0, 128, 0, 8, 513, 385, 4, 4, 2, 2, 257, 193) == _lib.WGRAD_S2
     assert route(128, 64, 64, 0, 128, 0, 8, 513, 385, 4, 4, 2, 2, 256, 193) == _lib.WGRAD_BF16
     assert route(128, 64, 64, 0, 128, 0, 8, 513, 385, 4, 4, 2, 2, 257, 192) == _lib.WGRAD_BF16
+
+
+_RESERVE_CHILD = r"""
+import json, os, sys
+sys.path.insert(0, sys.argv[1])
+import hr_viton_amd  # noqa: F401
+from hr_viton_amd import _lib
+lib = _lib.load()
+out = {}
+cus = lambda: int(lib.hrv_persistent_cus())      # noqa: E731
+# before any explicit set the grid follows the variable at every reload
+out["env0"] = cus()
+os.environ["HRV_RESERVE_CUS"] = "16"
+out["env16_before_reload"] = cus()
+_lib.reload_env()
+out["env16"] = cus()
+os.environ["HRV_RESERVE_CUS"] = "4000"
+_lib.reload_env()
+out["env4000"] = cus()
+del os.environ["HRV_RESERVE_CUS"]
+_lib.reload_env()
+out["env_unset"] = cus()
+# explicit
+out["set"] = []
+for k in (0, 16, 248, 4000):
+    out["set"].append([k, int(lib.hrv_set_reserved_cus(k)), cus()])
+lib.hrv_set_reserved_cus(16)
+out["bad"] = []
+for k in (-1, 4096):
+    rc = int(lib.hrv_set_reserved_cus(k))
+    out["bad"].append([k, rc, lib.hrv_last_error().decode(), cus()])
+# an explicit value outlives a reload, whatever the variable says
+os.environ["HRV_RESERVE_CUS"] = "248"
+_lib.reload_env()
+out["explicit_after_reload"] = cus()
+del os.environ["HRV_RESERVE_CUS"]
+_lib.reload_env()
+out["explicit_after_unset"] = cus()
+print("RESULT " + json.dumps(out))
+"""
+
+
+def test_reserved_cus_in_a_child_process(lib):
+    """hrv_set_reserved_cus / hrv_persistent_cus / HRV_RESERVE_CUS.  In a child process: an explicit set is sticky for the life of
+    the process (later reloads keep it), which must not leak into the tests that cut the grid through the environment.  Without a
+    GPU the library assumes 256 CUs, which is also what an MI355X has."""
+    import json
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if k != "HRV_RESERVE_CUS"}
+    r = subprocess.run([sys.executable, "-c", _RESERVE_CHILD, ROOT], env=env, cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
+    assert out["env0"] == 256
+    assert out["env16_before_reload"] == 256          # the variable is read once ...
+    assert (out["env16"], out["env4000"], out["env_unset"]) == (240, 8, 256)      # ... and again at every reload; never below 8
+    assert out["set"] == [[0, 0, 256], [16, 0, 240], [248, 0, 8], [4000, 0, 8]]
+    for k, rc, msg, cus in out["bad"]:
+        assert rc != 0 and "set_reserved_cus" in msg and str(k) in msg and cus == 240, (k, rc, msg, cus)
+    assert out["explicit_after_reload"] == 240 and out["explicit_after_unset"] == 240
