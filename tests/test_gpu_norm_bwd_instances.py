@@ -38,11 +38,14 @@ class _Buf:
         return bool((self.t[..., m] == POISON).all())
 
 
-def _one_norm(case, N, H, W, Cn, seed, x, dx):
-    """descriptor of one norm of ``case`` over x (a _Buf or an (lo, hi) pair of them) + everything it writes"""
+def _one_norm(case, N, H, W, Cn, seed, x, dx, given=None):
+    """descriptor of one norm of ``case`` over x (a _Buf or an (lo, hi) pair of them) + everything it writes.  The operands are
+    drawn from ``seed``, or taken from ``given`` (tests/test_gpu_norm_exact.py): mean, rstd, dout, and what the kind carries of
+    z, ns, out, slope, g1p; optionally dns0, an old noise-scale gradient that is accumulated into"""
     from hr_viton_amd import _lib
     g = torch.Generator(device="cuda").manual_seed(seed)
     rnd = lambda *s: torch.randn(*s, device="cuda", generator=g)
+    pick = lambda name, draw: given[name].to("cuda", torch.float32).contiguous() if given is not None else draw()
     mixed = case.kind != "f32"
     d = _lib.hrv_norm_bwd_t()
     d.N, d.H, d.W, d.C = N, H, W, Cn
@@ -53,16 +56,18 @@ def _one_norm(case, N, H, W, Cn, seed, x, dx):
         d.x_up_channels, d.x2, d.x2_cstride, d.x2_coff = lo.C, hi.t.data_ptr(), hi.cs, hi.coff
     else:
         x.set(d, "x")
-    mean, rstd = rnd(N, Cn) * 0.3, rnd(N, Cn).abs() + 0.5
+    mean, rstd = pick("mean", lambda: rnd(N, Cn) * 0.3), pick("rstd", lambda: rnd(N, Cn).abs() + 0.5)
     d.mean, d.rstd = mean.data_ptr(), rstd.data_ptr()
     keep += [mean, rstd]
     noise = case.kind != "inorm"
     dns = None
     if noise:
-        z, ns, dns = rnd(N, W, H), rnd(Cn) * 0.1, torch.full((Cn,), POISON, device="cuda")
+        z, ns, dns = pick("z", lambda: rnd(N, W, H)), pick("ns", lambda: rnd(Cn) * 0.1), torch.full((Cn,), POISON, device="cuda")
+        if given is not None and "dns0" in given:
+            dns, d.dns_accumulate = given["dns0"].to("cuda", torch.float32).contiguous(), 1
         d.noise_z, d.noise_scale, d.dnoise_scale = z.data_ptr(), ns.data_ptr(), dns.data_ptr()
         keep += [z, ns]
-    dout_v = rnd(N, H, W, Cn) * 0.1
+    dout_v = pick("dout", lambda: rnd(N, H, W, Cn) * 0.1)
     dgb = None
     if case.kind == "spade":          # dout lives in the dbeta half of a bf16 [dgamma | dbeta]
         dgb = _Buf(N, H, W, 2 * Cn, True)
@@ -74,16 +79,16 @@ def _one_norm(case, N, H, W, Cn, seed, x, dx):
     else:
         io = {"f32": (False, False), "bf16": (True, True), "mixed": (True, False)}[case.io]
         dout = _Buf(N, H, W, Cn, io[0], fill=dout_v)
-        out = _Buf(N, H, W, Cn, io[1], fill=rnd(N, H, W, Cn))
+        out = _Buf(N, H, W, Cn, io[1], fill=pick("out", lambda: rnd(N, H, W, Cn)))
         dout.set(d, "dout")
         out.set(d, "out")
-        d.dout_bf16, d.out_bf16, d.act, d.act_slope = int(io[0]), int(io[1]), ACT_LRELU, 0.2
+        d.dout_bf16, d.out_bf16, d.act, d.act_slope = int(io[0]), int(io[1]), ACT_LRELU, given["slope"] if given is not None else 0.2
         keep += [dout, out]
         if case.kind == "f32":
             dgb = _Buf(N, H, W, 2 * Cn, False)
             dgb.set(d, "dgb")
     if case.kind != "inorm":
-        g1p = _Buf(N, H, W, Cn, case.g1p == "bf16", fill=1.0 + rnd(N, H, W, Cn) * 0.2)
+        g1p = _Buf(N, H, W, Cn, case.g1p == "bf16", fill=pick("g1p", lambda: 1.0 + rnd(N, H, W, Cn) * 0.2))
         g1p.set(d, "g1p")
         d.g1p_bf16 = int(g1p.bf16)
         keep.append(g1p)
