@@ -240,6 +240,12 @@ SYMBOLS = {
     "hrv_adam_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i32, _f, _vp]),
     "hrv_adam_hyper_f32": (C.c_int, [_vp, _vp, _f, _f, _vp, _vp]),
     "hrv_adam_dev_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _f, _f, _f, _f, _f, _vp]),
+    "hrv_grad_guard_slots": (C.c_int, []),
+    "hrv_grad_sumsq_f32": (C.c_int, [_vp, _i64, _vp, _vp, _vp]),
+    "hrv_grad_guard_finalize": (C.c_int, [_vp, _vp, _f, _f, _i32, _vp, _vp]),
+    "hrv_grad_guard_finalize_hyper": (C.c_int, [_vp, _vp, _f, _f, _i32, _vp, _vp, _vp, _f, _f, _vp, _vp]),
+    "hrv_adam_guarded_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i32, _f, _vp, _vp]),
+    "hrv_adam_dev_guarded_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _f, _f, _f, _f, _f, _vp, _vp]),
     "hrv_spectral_norm_f32": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _f, _vp, _vp, _vp]),
     "hrv_spectral_norm_bwd_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp]),
     "hrv_spectral_norm_batched_f32": (C.c_int, [_vp, _i32, _i32, _f, _vp, _vp]),

@@ -5,6 +5,7 @@
 // (The InstanceNorm / SPADE backward is norm_bwd.hip.)
 #include <string.h>
 
+#include "adam_body.h"
 #include "hrv_common.h"
 
 namespace hrv {
@@ -316,22 +317,12 @@ __global__ void add_slice_bf16_kernel(const unsigned short* __restrict__ a, int 
 
 // ---------------------------------------------------------------------------
 // Adam (torch.optim.Adam semantics: no amsgrad, optional L2 weight decay), fused over one
-// flat buffer.  step_size = lr / (1 - b1^t);  denom = sqrt(v)/sqrt(1 - b2^t) + eps
+// flat buffer.  The update itself is adam_body.h (shared with the guarded kernels of grad_guard.hip).
 // ---------------------------------------------------------------------------
 __global__ void adam_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
                             float* __restrict__ v, size_t n, float lr, float b1, float b2, float eps, float wd,
                             float bc1, float bc2_sqrt, float gscale) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    float gi = g[i] * gscale;
-    const float wi = w[i];
-    if (wd != 0.f) gi += wd * wi;
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-    m[i] = mi;
-    v[i] = vi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    w[i] = wi - (lr / bc1) * (mi / denom);
-  }
+  adam_update<false>(w, g, m, v, n, (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale, nullptr);
 }
 
 // The same update with its step-dependent scalars on the DEVICE (hipGraph-capturable training iteration: a replay must not
@@ -352,17 +343,7 @@ __global__ void adam_dev_kernel(float* __restrict__ w, const float* __restrict__
                                 float* __restrict__ v, size_t n, const float* __restrict__ hyper, float b1, float b2, float eps,
                                 float wd, float gscale) {
   const float lr = hyper[0], bc1 = hyper[1], bc2_sqrt = hyper[2];
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    float gi = g[i] * gscale;
-    const float wi = w[i];
-    if (wd != 0.f) gi += wd * wi;
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-    m[i] = mi;
-    v[i] = vi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    w[i] = wi - (lr / bc1) * (mi / denom);
-  }
+  adam_update<false>(w, g, m, v, n, (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale, nullptr);
 }
 
 // ---------------------------------------------------------------------------

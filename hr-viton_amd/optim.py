@@ -40,15 +40,57 @@ def _flat_order(ps):
 
 
 class Adam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, grad_sync=None, device_step=False):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, grad_sync=None, device_step=False,
+                 max_grad_norm=None, skip_nonfinite=False):
         """``device_step``: the step count and the learning rate live on the device (hrv_adam_hyper_f32 / _dev_f32), so a
         hipGraph-captured iteration (graph.GraphedTrainStep) keeps counting and follows the scheduler; every parameter must
-        then receive a gradient in every iteration."""
+        then receive a gradient in every iteration (or in none at all, without weight decay: it is then left as it is).
+
+        ``max_grad_norm`` / ``skip_nonfinite``: the guarded step (csrc/grad_guard.hip).  With either set, step() first reduces the
+        whole flat gradient buffer of a group to its 2-norm (fp64 accumulation, deterministic) and a count of non-finite elements,
+        and the Adam launch consumes the decision ON THE DEVICE: no host synchronisation, capturable in a hipGraph.
+        ``max_grad_norm``: the gradients of a group are scaled by min(1, max_grad_norm / (norm + 1e-6)), the expression of
+        torch.nn.utils.clip_grad_norm_ (with ``skip_nonfinite`` off a non-finite norm propagates into the weights, as with
+        ``error_if_nonfinite=False`` there).  ``skip_nonfinite``: a step whose gradients hold an Inf / NaN, or whose norm overflows
+        fp32, touches neither weights nor moments nor the step count; it needs ``device_step=True`` (a host-side step count
+        cannot learn of a skip without a synchronisation).  With both at their defaults nothing is allocated or launched for it.
+        The norm is taken per parameter group (one flat buffer each), over the all-reduced and averaged gradients under data
+        parallelism, so every rank decides alike.
+
+        The guard covers the optimizer's state: weights, moments, step count.  State a forward pass wrote BEFORE the gradient
+        existed is not rolled back by a skip: BatchNorm running statistics (the condition generator), spectral norm's ``u``."""
         defaults = dict(lr=lr, betas=(float(betas[0]), float(betas[1])), eps=eps, weight_decay=weight_decay)
         super().__init__(params, defaults)
         self.grad_sync = grad_sync
         self._flat = {}
         self.device_step = bool(device_step)
+        self.max_grad_norm = float(max_grad_norm) if max_grad_norm else None
+        if self.max_grad_norm is not None and not self.max_grad_norm > 0.0:
+            raise ops.HrvError(f"Adam: max_grad_norm must be positive (None or 0 switches clipping off), got {max_grad_norm}")
+        self.skip_nonfinite = bool(skip_nonfinite)
+        if self.skip_nonfinite and not self.device_step:
+            raise ops.HrvError("Adam: skip_nonfinite=True needs the step count on the device; build the optimizer with "
+                               "device_step=True")
+        self.guarded = self.max_grad_norm is not None or self.skip_nonfinite
+
+    @property
+    def guard_record(self):
+        """The device-side guard record of parameter group 0 (int32 [16]; layout: include/hrviton_hip.h), for callers that must
+        not synchronise; ``guard_records()`` lists every group's.  None before the first step, or with the guard off."""
+        st = self._flat.get(0)
+        return st.get("guard") if st else None
+
+    def guard_records(self):
+        return [(self._flat.get(gi) or {}).get("guard") for gi in range(len(self.param_groups))]
+
+    def guard_stats(self, group: int = 0):
+        """The guard record of one parameter group as Python numbers (ONE host copy, which synchronises): ``norm`` and ``scale`` of
+        the last step, ``apply`` (0: it was skipped), its ``nonfinite`` element count, its un-scaled ``sumsq``, and the running
+        totals ``steps`` / ``skipped`` / ``clipped``.  None with the guard off or before the first step."""
+        st = self._flat.get(group)
+        if not st or "guard" not in st:
+            return None
+        return T.guard_read(st["guard"])
 
     def push_lr(self):
         """device_step: copy each group's current learning rate to its device scalar (call BEFORE replaying a captured
@@ -79,6 +121,8 @@ class Adam(torch.optim.Optimizer):
         # in some iteration (skipped below) falls behind the others, and its bias correction must use ITS count
         st = dict(w=w, m=torch.zeros_like(w), v=torch.zeros_like(w), g=torch.zeros_like(w), spans=spans, step=0,
                   steps=[0] * len(spans))
+        if self.guarded:      # record + workspace exist before any step (a captured step() allocates nothing)
+            st["guard"], st["guard_part"], st["guard_cnt"] = T.guard_alloc(dev)
         self._flat[gi] = st
         # the backward plans write gradients straight into these slots (gen_train.grad_buffer / _acc)
         for p, off, k in spans:
@@ -117,7 +161,7 @@ class Adam(torch.optim.Optimizer):
             st = self._flat.get(gi) or self._setup(gi, group)
             g = st["g"]
             base = g.data_ptr()
-            skipped = []
+            skipped, missing = [], 0
             steps = st["steps"]
             for i, (p, off, k) in enumerate(st["spans"]):
                 src = self.grad_sync.grad_of(p) if self.grad_sync is not None else p.grad
@@ -126,18 +170,31 @@ class Adam(torch.optim.Optimizer):
                     # untouched): the fused launch covers whole runs of the flat buffer, so the span is snapshotted here
                     # and restored below
                     g[off:off + k].zero_()
+                    if self.device_step:
+                        # a parameter that has NEVER had a gradient (a block the configured generator does not use) rides along:
+                        # zero gradient on zero moments without weight decay is an exact no-op of the update.  One that had
+                        # gradients before would need its own step count: refused below.
+                        missing += steps[i] != 0 or group["weight_decay"] != 0
+                        st.setdefault("never", set()).add(i)
+                        continue
                     skipped.append((off, k, st["w"][off:off + k].clone(), st["m"][off:off + k].clone(),
                                     st["v"][off:off + k].clone()))
                 else:
+                    if self.device_step and i in st.get("never", ()):      # ... and one that rode along cannot join later
+                        missing += 1
                     steps[i] += 1
                     if src.data_ptr() != base + 4 * off:   # already produced in place by the backward plan otherwise
                         g[off:off + k].copy_(src.reshape(-1))
             st["step"] += 1
             b1, b2 = group["betas"]
+            if self.guarded:
+                # the padding between spans is zero (zeros_like; every writer takes a k-element view): the sum over the buffer
+                # is the sum over the parameters' elements
+                T.grad_sumsq(g, st["guard_part"], st["guard_cnt"])
             if self.device_step:
-                if skipped:
+                if missing:
                     raise ops.HrvError("device_step Adam: every parameter needs a gradient in every iteration (one device-side "
-                                       f"step count serves the whole buffer); {len(skipped)} parameter(s) had none")
+                                       f"step count serves the whole buffer); {missing} parameter(s) had none")
                 if "step_dev" not in st:
                     dev = g.device
                     st["step_dev"] = torch.full((1,), st["step"] - 1, dtype=torch.int32, device=dev)
@@ -145,9 +202,17 @@ class Adam(torch.optim.Optimizer):
                     st["hyper"] = torch.zeros(3, dtype=torch.float32, device=dev)
                 if not torch.cuda.is_current_stream_capturing():
                     st["lr_dev"].fill_(float(group["lr"]))       # (a captured iteration reads what push_lr() wrote)
-                T.adam_step_dev(st["w"], g, st["m"], st["v"], st["step_dev"], st["lr_dev"], st["hyper"], b1, b2, group["eps"],
-                                group["weight_decay"], world_scale)
+                if self.guarded:
+                    T.grad_guard_finalize(st["guard_part"], st["guard_cnt"], st["guard"], world_scale, self.max_grad_norm,
+                                          self.skip_nonfinite, st["step_dev"], st["lr_dev"], st["hyper"], b1, b2)
+                    T.adam_step_dev_guarded(st["w"], g, st["m"], st["v"], st["hyper"], b1, b2, group["eps"], group["weight_decay"],
+                                            world_scale, st["guard"])
+                else:
+                    T.adam_step_dev(st["w"], g, st["m"], st["v"], st["step_dev"], st["lr_dev"], st["hyper"], b1, b2, group["eps"],
+                                    group["weight_decay"], world_scale)
                 continue
+            if self.guarded:      # (clipping alone: every launch below reads the same scale)
+                T.grad_guard_finalize(st["guard_part"], st["guard_cnt"], st["guard"], world_scale, self.max_grad_norm, False)
             # one launch per run of consecutive spans that share a step count (a skipped span rides along with either
             # neighbour: it is restored afterwards) -- ONE launch over the whole buffer unless some parameter fell behind
             runs, n_sp = [], len(st["spans"])
@@ -167,8 +232,12 @@ class Adam(torch.optim.Optimizer):
             if len(runs) == 1 and len(skipped) == 0:
                 runs = [(0, g.numel(), runs[0][2])]
             for a, b, cnt in runs:
-                T.adam_step(st["w"][a:b], g[a:b], st["m"][a:b], st["v"][a:b], float(group["lr"]), b1, b2, group["eps"],
-                            group["weight_decay"], cnt, world_scale)
+                if self.guarded:
+                    T.adam_step_guarded(st["w"][a:b], g[a:b], st["m"][a:b], st["v"][a:b], float(group["lr"]), b1, b2, group["eps"],
+                                        group["weight_decay"], cnt, world_scale, st["guard"])
+                else:
+                    T.adam_step(st["w"][a:b], g[a:b], st["m"][a:b], st["v"][a:b], float(group["lr"]), b1, b2, group["eps"],
+                                group["weight_decay"], cnt, world_scale)
             for off, k, w0, m0, v0 in skipped:
                 st["w"][off:off + k].copy_(w0)
                 st["m"][off:off + k].copy_(m0)
@@ -190,8 +259,9 @@ class Adam(torch.optim.Optimizer):
             pos = {id(p): i for i, (p, _, _) in enumerate(st["spans"])} if st else {}
             ids = []
             dev_step = int(st["step_dev"].item()) if st and "step_dev" in st else None      # ONE host sync per group
+            never = st.get("never", ()) if st else ()      # (device_step: parameters that ride along without a gradient)
             for p in group["params"]:
-                if st and id(p) in spans:
+                if st and id(p) in spans and pos[id(p)] not in never:      # like torch: no state for a parameter never stepped
                     off, k = spans[id(p)]
                     stp = dev_step if dev_step is not None else st["steps"][pos[id(p)]]
                     state[idx] = {"step": torch.tensor(float(stp)),
@@ -230,3 +300,52 @@ class Adam(torch.optim.Optimizer):
                 # bias correction from the LOADED count, not from the one this optimizer had reached before the load
                 st["step_dev"].fill_(int(st["step"]))
                 st["lr_dev"].fill_(float(group["lr"]))
+
+
+# ------------------------------------------------------------------ the training scripts' side of the guard
+def add_guard_args(parser):
+    """--max_grad_norm_G / --max_grad_norm_D / --skip_nonfinite of train_generator.py and train_condition.py.  The options appear
+    in the parsed namespace only when given (argparse.SUPPRESS): a run without them prints the option line it always printed;
+    guard_kwargs() reads them with their defaults (0 / 0 / off)."""
+    import argparse
+    parser.add_argument("--max_grad_norm_G", type=float, default=argparse.SUPPRESS,
+                        help="clip the generator's gradient 2-norm to this value on the device (0: off)")
+    parser.add_argument("--max_grad_norm_D", type=float, default=argparse.SUPPRESS,
+                        help="clip the discriminator's gradient 2-norm to this value on the device (0: off)")
+    parser.add_argument("--skip_nonfinite", action="store_true", default=argparse.SUPPRESS,
+                        help="skip, on the device, an optimizer step whose gradients hold an Inf / NaN (the optimizers then keep "
+                             "their step count and learning rate on the device)")
+
+
+def guard_kwargs(opt, which):
+    """Adam's keyword arguments for the ``which`` ("G" / "D") optimizer of a script; empty (the plain construction) without the
+    flags."""
+    kw = {}
+    max_norm = float(getattr(opt, "max_grad_norm_" + which, 0.0) or 0.0)
+    if max_norm > 0:
+        kw["max_grad_norm"] = max_norm
+    if getattr(opt, "skip_nonfinite", False):
+        kw.update(skip_nonfinite=True, device_step=True)
+    return kw
+
+
+def guard_scalars(opt_g, opt_d):
+    """[(tag, value)] of the guarded optimizers: Grad/norm_*, Grad/skipped_*, Grad/clipped_* (one host copy each; call only where
+    the script synchronises anyway).  Both optimizers are listed as soon as one of them is guarded; an unguarded one reports zeros."""
+    stats = [(sfx, o.guard_stats() if o is not None and o.guarded else None) for sfx, o in (("G", opt_g), ("D", opt_d))]
+    if all(st is None for _, st in stats):
+        return []
+    out = []
+    for key in ("norm", "skipped", "clipped"):
+        for sfx, st in stats:
+            out.append(("Grad/%s_%s" % (key, sfx), float(st[key]) if st else 0.0))
+    return out
+
+
+def guard_line(opt_g, opt_d):
+    """The tail of the scripts' printed line: '' without a guard."""
+    sc = dict(guard_scalars(opt_g, opt_d))
+    if not sc:
+        return ""
+    return ", gnorm_G: %.4g, gnorm_D: %.4g, skipped_G: %d, skipped_D: %d" % (sc["Grad/norm_G"], sc["Grad/norm_D"],
+                                                                             sc["Grad/skipped_G"], sc["Grad/skipped_D"])

@@ -874,6 +874,86 @@ def adam_step_dev(w: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Te
                                         beta2, eps, weight_decay, grad_scale, _stream()), "hrv_adam_dev_f32")
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# Guarded Adam step (csrc/grad_guard.hip): gradient norm, clipping and the skip of a non-finite step, decided on the device.
+# The guard record is GUARD_WORDS int32 words (layout: include/hrviton_hip.h); guard_read() decodes a host copy of it.
+# ---------------------------------------------------------------------------------------------------------------
+GUARD_NORM, GUARD_SCALE, GUARD_APPLY, GUARD_NONFINITE, GUARD_STEPS, GUARD_SKIPPED, GUARD_CLIPPED, GUARD_SUMSQ = 0, 1, 2, 3, 4, 5, 6, 8
+GUARD_WORDS = 16
+
+
+def guard_slots() -> int:
+    return int(_lib.load().hrv_grad_guard_slots())
+
+
+def guard_alloc(device) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(record int32 [GUARD_WORDS] zeroed, partial sums float64 [P], partial counts int32 [P]) for one flat buffer."""
+    P = guard_slots()
+    return (torch.zeros(GUARD_WORDS, dtype=torch.int32, device=device), torch.zeros(P, dtype=torch.float64, device=device),
+            torch.zeros(P, dtype=torch.int32, device=device))
+
+
+def guard_read(record: torch.Tensor) -> dict:
+    """The guard record as Python numbers (ONE device-to-host copy)."""
+    h = record.detach().cpu()
+    f = h.view(torch.float32)
+    return {"norm": float(f[GUARD_NORM]), "scale": float(f[GUARD_SCALE]), "apply": int(h[GUARD_APPLY]),
+            "nonfinite": int(h[GUARD_NONFINITE]), "steps": int(h[GUARD_STEPS]), "skipped": int(h[GUARD_SKIPPED]),
+            "clipped": int(h[GUARD_CLIPPED]), "sumsq": float(h.view(torch.float64)[GUARD_SUMSQ // 2])}
+
+
+def grad_sumsq(g: torch.Tensor, part: torch.Tensor, cnt: torch.Tensor):
+    """Per-slot sum of squares (fp64) and non-finite count of the flat fp32 buffer ``g`` (any contiguous slice: the pointer need
+    only be 4-byte aligned)."""
+    lib = _lib.load()
+    ops.require_cuda(g, "grad_sumsq(g)")
+    if g.dtype != torch.float32 or not g.is_contiguous() or g.numel() < 1:
+        raise ops.HrvError("grad_sumsq: a non-empty contiguous fp32 buffer is required")
+    P = guard_slots()
+    if part.dtype != torch.float64 or cnt.dtype != torch.int32 or part.numel() < P or cnt.numel() < P:
+        raise ops.HrvError(f"grad_sumsq: the workspace is {P} float64 sums and {P} int32 counts")
+    with _Timed("grad_guard", "grad_sumsq_f32", 0.0, 4.0 * g.numel()):
+        _lib.check(lib.hrv_grad_sumsq_f32(g.data_ptr(), g.numel(), part.data_ptr(), cnt.data_ptr(), _stream()), "hrv_grad_sumsq_f32")
+
+
+def grad_guard_finalize(part: torch.Tensor, cnt: torch.Tensor, record: torch.Tensor, grad_scale: float = 1.0,
+                        max_norm: Optional[float] = None, skip_nonfinite: bool = False, step_dev: Optional[torch.Tensor] = None,
+                        lr_dev: Optional[torch.Tensor] = None, hyper: Optional[torch.Tensor] = None, beta1: float = 0.0,
+                        beta2: float = 0.0):
+    """Partials -> guard record.  With ``step_dev`` / ``lr_dev`` / ``hyper`` it also does hrv_adam_hyper_f32's work, for applied
+    steps only (a skipped step does not advance the bias correction)."""
+    lib = _lib.load()
+    if record.dtype != torch.int32 or record.numel() < GUARD_WORDS:
+        raise ops.HrvError(f"grad_guard_finalize: the record is {GUARD_WORDS} int32 words")
+    mx = float(max_norm) if max_norm else 0.0
+    if step_dev is None:
+        _lib.check(lib.hrv_grad_guard_finalize(part.data_ptr(), cnt.data_ptr(), grad_scale, mx, int(bool(skip_nonfinite)),
+                                               record.data_ptr(), _stream()), "hrv_grad_guard_finalize")
+    else:
+        _lib.check(lib.hrv_grad_guard_finalize_hyper(part.data_ptr(), cnt.data_ptr(), grad_scale, mx, int(bool(skip_nonfinite)),
+                                                     record.data_ptr(), step_dev.data_ptr(), lr_dev.data_ptr(), beta1, beta2,
+                                                     hyper.data_ptr(), _stream()), "hrv_grad_guard_finalize_hyper")
+
+
+def adam_step_guarded(w: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, lr: float, beta1: float, beta2: float,
+                      eps: float, weight_decay: float, step: int, grad_scale: float, record: torch.Tensor):
+    """adam_step reading the guard record: nothing is touched when apply == 0, the gradient is (g * grad_scale) * scale otherwise."""
+    lib = _lib.load()
+    with _Timed("adam", "adam_f32", 0.0, 28.0 * w.numel()):
+        _lib.check(lib.hrv_adam_guarded_f32(w.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), w.numel(), lr, beta1, beta2, eps,
+                                            weight_decay, step, grad_scale, record.data_ptr(), _stream()), "hrv_adam_guarded_f32")
+
+
+def adam_step_dev_guarded(w: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, hyper: torch.Tensor, beta1: float,
+                          beta2: float, eps: float, weight_decay: float, grad_scale: float, record: torch.Tensor):
+    """The device-step launch alone (grad_guard_finalize with step_dev / lr_dev / hyper has already counted the step)."""
+    lib = _lib.load()
+    with _Timed("adam", "adam_f32", 0.0, 28.0 * w.numel()):
+        _lib.check(lib.hrv_adam_dev_guarded_f32(w.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), w.numel(), hyper.data_ptr(),
+                                                beta1, beta2, eps, weight_decay, grad_scale, record.data_ptr(), _stream()),
+                   "hrv_adam_dev_guarded_f32")
+
+
 def spectral_sigma(w_orig: torch.Tensor, u: torch.Tensor, v: torch.Tensor, power_iterations: int,
                    eps: float = 1e-12) -> torch.Tensor:
     """In-place power iteration on (u, v) + sigma (device scalar tensor [1])."""

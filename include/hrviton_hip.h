@@ -404,6 +404,53 @@ int hrv_adam_f32(float* w, const float* g, float* m, float* v, int64_t n, float 
 int hrv_adam_hyper_f32(int32_t* step_dev, const float* lr_dev, float beta1, float beta2, float* hyper_dev, hrv_stream_t stream);
 int hrv_adam_dev_f32(float* w, const float* g, float* m, float* v, int64_t n, const float* hyper_dev, float beta1, float beta2,
                      float eps, float weight_decay, float grad_scale, hrv_stream_t stream);
+/* Guarded Adam step: gradient norm, clipping and the skip of a non-finite step, decided ON THE DEVICE (no host read, capturable).
+ *
+ * hrv_grad_sumsq_f32: one pass over g[0, n) (any 4-byte-aligned pointer, any n >= 1; nothing outside [0, n) is read).  Slot s of
+ * the hrv_grad_guard_slots() slots receives part[s] = sum of (double)g[i]^2 over its elements and cnt[s] = how many of them are
+ * non-finite (exponent field all ones).  The slot count is a compile-time constant of the library, the element -> slot rule and
+ * every summation order are fixed and no atomics are used: the same buffer gives the same bits in every run and on every card.
+ *
+ * hrv_grad_guard_finalize: one block sums the slots in fixed order and fills the guard record, HRV_GUARD_WORDS 32-bit words:
+ *   [HRV_GUARD_NORM]      f32  grad_scale * sqrt(sumsq), rounded once to fp32
+ *   [HRV_GUARD_SCALE]     f32  min(1, max_norm / (norm + 1e-6)) in fp32 (torch.nn.utils.clip_grad_norm_; a NaN norm gives NaN, as
+ *                              there); exactly 1.0f when clipping is off (max_norm <= 0)
+ *   [HRV_GUARD_APPLY]     i32  0 when skip_nonfinite is set and (the count is non-zero or norm is not finite in fp32), else 1
+ *   [HRV_GUARD_NONFINITE] i32  this step's count of non-finite elements
+ *   [HRV_GUARD_STEPS]     i32  running total: steps seen
+ *   [HRV_GUARD_SKIPPED]   i32  running total: steps with apply == 0
+ *   [HRV_GUARD_CLIPPED]   i32  running total: applied steps with scale < 1
+ *   [7]                        reserved (0)
+ *   [HRV_GUARD_SUMSQ, +1] f64  the un-scaled sum of squares
+ *   [10 .. 15]                 reserved
+ * The three totals continue from what the record holds: zero it once before the first step.
+ * hrv_grad_guard_finalize_hyper additionally does the work of hrv_adam_hyper_f32, but ONLY when apply == 1: a skipped step leaves
+ * step_dev and hyper_dev alone, so it does not advance the bias correction.
+ *
+ * hrv_adam_guarded_f32 / hrv_adam_dev_guarded_f32: hrv_adam_f32 / hrv_adam_dev_f32 reading the record.  apply == 0: the launch
+ * touches nothing.  Otherwise the gradient is (g * grad_scale) * scale; with scale == 1.0f the result has the bits of the plain
+ * kernel. */
+#define HRV_GUARD_NORM 0
+#define HRV_GUARD_SCALE 1
+#define HRV_GUARD_APPLY 2
+#define HRV_GUARD_NONFINITE 3
+#define HRV_GUARD_STEPS 4
+#define HRV_GUARD_SKIPPED 5
+#define HRV_GUARD_CLIPPED 6
+#define HRV_GUARD_SUMSQ 8
+#define HRV_GUARD_WORDS 16
+int hrv_grad_guard_slots(void);
+int hrv_grad_sumsq_f32(const float* g, int64_t n, double* part, int32_t* cnt, hrv_stream_t stream);
+int hrv_grad_guard_finalize(const double* part, const int32_t* cnt, float grad_scale, float max_norm, int32_t skip_nonfinite,
+                            int32_t* record, hrv_stream_t stream);
+int hrv_grad_guard_finalize_hyper(const double* part, const int32_t* cnt, float grad_scale, float max_norm, int32_t skip_nonfinite,
+                                  int32_t* record, int32_t* step_dev, const float* lr_dev, float beta1, float beta2,
+                                  float* hyper_dev, hrv_stream_t stream);
+int hrv_adam_guarded_f32(float* w, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                         float weight_decay, int32_t step, float grad_scale, const int32_t* record, hrv_stream_t stream);
+int hrv_adam_dev_guarded_f32(float* w, const float* g, float* m, float* v, int64_t n, const float* hyper_dev, float beta1,
+                             float beta2, float eps, float weight_decay, float grad_scale, const int32_t* record,
+                             hrv_stream_t stream);
 /* torch spectral_norm (SpectralNorm.compute_weight): `power_iterations` rounds of
  * v<-normalize(W^T u), u<-normalize(W v) in place (eps 1e-12), then sigma = u.(W v).
  * W is [R][K] = weight_orig.reshape(Cout,-1); wv_scratch holds R floats.

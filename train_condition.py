@@ -44,7 +44,7 @@ from hr_viton_amd.gen_train import attach_grad_sync  # noqa: E402
 from hr_viton_amd.losses import L1Loss  # noqa: E402
 from hr_viton_amd.networks import (ConditionGenerator, GANLoss, VGGLoss, define_D, load_checkpoint,  # noqa: E402
                                    save_checkpoint)
-from hr_viton_amd.optim import Adam  # noqa: E402
+from hr_viton_amd.optim import Adam, add_guard_args, guard_kwargs, guard_line, guard_scalars  # noqa: E402
 from hr_viton_amd.parallel import broadcast_module  # noqa: E402
 from hr_viton_amd.pipeline import condition_train_step  # noqa: E402
 from hr_viton_amd.validate import condition_validation_iou, val_items_loader, validation_due  # noqa: E402
@@ -113,6 +113,7 @@ def get_opt(argv=None):
     p.add_argument("--val_items", type=int, default=2000, help="test items scored per val/iou pass (the reference's 2000)")
     p.add_argument("--board", action="store_true",
                    help="every --tensorboard_count steps record the loss scalars and the image grids (train_condition.py:362-436)")
+    add_guard_args(p)
     opt = p.parse_args(argv)
     return opt
 
@@ -172,6 +173,7 @@ class _Validation(object):
         self.loader = None
         self.board = viz.BoardLog(os.path.join(opt.tensorboard_dir, opt.name))
         self.vis = None
+        self.opt_g = self.opt_d = None      # the optimizers whose guard records ride along with the loss scalars (main sets them)
 
     def batches(self):
         opt = self.opt
@@ -212,6 +214,8 @@ class _Validation(object):
             if key in losses and not (key == "vgg" and opt.no_vgg_loss):
                 v = losses[key]
                 self.board.add_scalar(tag, float(v.detach()) if torch.is_tensor(v) else float(v), s)
+        for tag, val in guard_scalars(self.opt_g, self.opt_d):      # (nothing without --max_grad_norm_* / --skip_nonfinite)
+            self.board.add_scalar(tag, val, s)
         self.board.add_image("train_images", viz.condition_grid(batch, aux, quant=viz.TRUNC, count=1)[0], s)
         if not opt.no_test_visualize and opt.num_test_visualize > 0:
             vb = self.vis_batch()
@@ -261,8 +265,8 @@ def main(argv=None):
                              "or --no_vgg_loss, or --vgg_random_init for plumbing runs")
         crit_vgg.to(dev)
         broadcast_module(crit_vgg)
-    opt_g = Adam(tocg.parameters(), lr=opt.G_lr, betas=(0.5, 0.999))
-    opt_d = Adam(D.parameters(), lr=opt.D_lr, betas=(0.5, 0.999))
+    opt_g = Adam(tocg.parameters(), lr=opt.G_lr, betas=(0.5, 0.999), **guard_kwargs(opt, "G"))
+    opt_d = Adam(D.parameters(), lr=opt.D_lr, betas=(0.5, 0.999), **guard_kwargs(opt, "D"))
     sync_g = opt_g.make_grad_sync() if world > 1 else None
     sync_d = opt_d.make_grad_sync() if world > 1 else None
     for s in (sync_g, sync_d):
@@ -273,6 +277,8 @@ def main(argv=None):
         loader = _rank_loader(opt, per_rank, rank, world)
     last = opt.keep_step if not opt.max_steps else min(opt.keep_step, opt.load_step + opt.max_steps)
     validation = _Validation(opt, dev) if rank == 0 else None
+    if validation is not None:
+        validation.opt_g, validation.opt_d = opt_g, opt_d
     for step in range(opt.load_step, last):
         t0 = time.time()
         record = opt.board and validation is not None and validation_due(step, opt.tensorboard_count)       # :362
@@ -298,7 +304,7 @@ def main(argv=None):
             print("step: %8d, time: %.3f\nloss G: %.4f, L1_cloth loss: %.4f, VGG loss: %.4f, TV loss: %.4f CE: %.4f, "
                   "G GAN: %.4f\nloss D: %.4f, D real: %.4f, D fake: %.4f"
                   % (step + 1, t, f("loss_G"), f("l1"), f("vgg"), f("tv"), f("ce"), f("g_gan"), f("loss_D"), f("d_real"),
-                     f("d_fake")), flush=True)
+                     f("d_fake")) + guard_line(opt_g, opt_d).replace(", ", "\n", 1), flush=True)
         if (step + 1) % opt.save_count == 0 and rank == 0:
             save_checkpoint(tocg, os.path.join(opt.checkpoint_dir, opt.name, "tocg_step_%06d.pth" % (step + 1)), opt)
             save_checkpoint(D, os.path.join(opt.checkpoint_dir, opt.name, "D_step_%06d.pth" % (step + 1)), opt)

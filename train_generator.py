@@ -47,7 +47,7 @@ from hr_viton_amd.gen_train import attach_grad_sync  # noqa: E402
 from hr_viton_amd.losses import GANLoss, L1Loss  # noqa: E402
 from hr_viton_amd.network_generator import MultiscaleDiscriminator, SPADEGenerator  # noqa: E402
 from hr_viton_amd.networks import ConditionGenerator  # noqa: E402
-from hr_viton_amd.optim import Adam  # noqa: E402
+from hr_viton_amd.optim import Adam, add_guard_args, guard_kwargs, guard_line, guard_scalars  # noqa: E402
 from hr_viton_amd.parallel import broadcast_module  # noqa: E402
 from hr_viton_amd.pipeline import generator_train_step, make_generator_inputs  # noqa: E402
 from hr_viton_amd.validate import (generator_validation_lpips, load_validation_lpips, val_items_loader,  # noqa: E402
@@ -129,6 +129,7 @@ def get_opt(argv=None):
     p.add_argument("--val_batch_size", type=int, default=1, help="batch of the test/LPIPS pass (the reference's 1)")
     p.add_argument("--board", action="store_true",
                    help="every --tensorboard_count steps record the loss scalars and the image grids (train_generator.py:364-478)")
+    add_guard_args(p)
     opt = p.parse_args(argv)
     opt.gpu_ids = [int(s) for s in str(opt.gpu_ids).split(",") if s.strip() and int(s) >= 0]
     return opt
@@ -165,6 +166,7 @@ class _Validation(object):
         self.loader, self.model, self.tried = None, None, False
         self.board = viz.BoardLog(os.path.join(opt.tensorboard_dir, opt.name))
         self.vis = None
+        self.opt_g = self.opt_d = None      # the optimizers whose guard records ride along with the loss scalars (main sets them)
 
     def vis_batch(self):
         """The test-visualisation batch (:383-395): the first --num_test_visualize test items with the unpaired cloth, loaded once."""
@@ -191,6 +193,8 @@ class _Validation(object):
         self.board.add_scalar("Loss/dis", float(sum(dis).mean()), s)
         self.board.add_scalar("Loss/dis/adv_fake", float(losses["D_Fake"].mean()), s)
         self.board.add_scalar("Loss/dis/adv_real", float(losses["D_Real"].mean()), s)
+        for tag, val in guard_scalars(self.opt_g, self.opt_d):      # (nothing without --max_grad_norm_* / --skip_nonfinite)
+            self.board.add_scalar(tag, val, s)
         if opt.num_test_visualize > 0:
             vb = self.vis_batch()
             fields, out = viz.generator_fields(opt, tocg, generator, vb)
@@ -275,8 +279,8 @@ def main(argv=None):
         crit_vgg.to(dev)
         broadcast_module(crit_vgg)
 
-    opt_g = Adam(generator.parameters(), lr=opt.G_lr, betas=(0.0, 0.9))
-    opt_d = Adam(discriminator.parameters(), lr=opt.D_lr, betas=(0.0, 0.9))
+    opt_g = Adam(generator.parameters(), lr=opt.G_lr, betas=(0.0, 0.9), **guard_kwargs(opt, "G"))
+    opt_d = Adam(discriminator.parameters(), lr=opt.D_lr, betas=(0.0, 0.9), **guard_kwargs(opt, "D"))
     # in-place bucketed all-reduce on the optimizers' flat gradient buffers, fired from inside the backward
     sync_g = opt_g.make_grad_sync() if world > 1 else None
     sync_d = opt_d.make_grad_sync() if world > 1 else None
@@ -299,6 +303,8 @@ def main(argv=None):
     if opt.max_steps:
         last = min(last, opt.load_step + opt.max_steps)
     validation = _Validation(opt, dev) if rank == 0 else None
+    if validation is not None:
+        validation.opt_g, validation.opt_d = opt_g, opt_d
     for step in range(opt.load_step, last):
         t0 = time.time()
         if loader is None:
@@ -320,7 +326,8 @@ def main(argv=None):
             ld = sum(v.item() for k, v in losses.items() if k.startswith("D_"))
             lg = sum(v.item() for k, v in losses.items() if not k.startswith("D_"))
             print("step: %8d, time: %.3f, G_loss: %.4f, G_adv_loss: %.4f, D_loss: %.4f, D_fake_loss: %.4f, D_real_loss: %.4f"
-                  % (step + 1, t, lg, losses["GAN"].item(), ld, losses["D_Fake"].item(), losses["D_Real"].item()), flush=True)
+                  % (step + 1, t, lg, losses["GAN"].item(), ld, losses["D_Fake"].item(), losses["D_Real"].item())
+                  + guard_line(opt_g, opt_d), flush=True)
         if (step + 1) % opt.save_count == 0 and rank == 0:
             save_checkpoint(generator, os.path.join(opt.checkpoint_dir, opt.name, "gen_step_%06d.pth" % (step + 1)), opt)
             save_checkpoint(discriminator, os.path.join(opt.checkpoint_dir, opt.name, "dis_step_%06d.pth" % (step + 1)), opt)
