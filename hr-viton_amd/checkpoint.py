@@ -45,8 +45,9 @@ def save_training_state(path, modules, optimizers=None, schedulers=None, step=0,
             "extra": extra or {}}
     for k, o in blob["optimizers"].items():
         for ent in o["state"].values():
-            for n in ("exp_avg", "exp_avg_sq"):
-                ent[n] = ent[n].cpu()
+            for n in ("exp_avg", "exp_avg_sq", "ema"):      # ("ema": optim.Adam(ema_decay=) only)
+                if n in ent:
+                    ent[n] = ent[n].cpu()
     torch.save(blob, path)
 
 

@@ -429,12 +429,13 @@ def define_D(input_nc, ndf=64, n_layers_D=3, norm="instance", use_sigmoid=False,
     return netD
 
 
-def save_checkpoint(model, save_path, opt=None):
-    """networks.py:411-417 -- torch.save of the CPU state_dict (same file format)."""
+def save_checkpoint(model, save_path, opt=None, state_dict=None):
+    """networks.py:411-417 -- torch.save of the CPU state_dict (same file format).  ``state_dict``: save this one instead of
+    ``model.state_dict()`` (optim.Adam.ema_state_dict(model): the averaged weights under the model's keys)."""
     d = os.path.dirname(save_path)
     if d and not os.path.exists(d):
         os.makedirs(d)
-    sd = model.state_dict()
+    sd = model.state_dict() if state_dict is None else state_dict
     out = type(sd)((k, v.detach().cpu()) for k, v in sd.items())
     if hasattr(sd, "_metadata"):
         out._metadata = sd._metadata      # spectral-norm version entries travel with the file

@@ -4,6 +4,7 @@ first step; gradients are gathered into a flat buffer (or taken from a ``GradSyn
 buckets).  LambdaLR and friends work unchanged (it is a torch.optim.Optimizer)."""
 from __future__ import annotations
 
+import contextlib
 
 import torch
 
@@ -41,7 +42,7 @@ def _flat_order(ps):
 
 class Adam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, grad_sync=None, device_step=False,
-                 max_grad_norm=None, skip_nonfinite=False):
+                 max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=False):
         """``device_step``: the step count and the learning rate live on the device (hrv_adam_hyper_f32 / _dev_f32), so a
         hipGraph-captured iteration (graph.GraphedTrainStep) keeps counting and follows the scheduler; every parameter must
         then receive a gradient in every iteration (or in none at all, without weight decay: it is then left as it is).
@@ -58,7 +59,18 @@ class Adam(torch.optim.Optimizer):
         parallelism, so every rank decides alike.
 
         The guard covers the optimizer's state: weights, moments, step count.  State a forward pass wrote BEFORE the gradient
-        existed is not rolled back by a skip: BatchNorm running statistics (the condition generator), spectral norm's ``u``."""
+        existed is not rolled back by a skip: BatchNorm running statistics (the condition generator), spectral norm's ``u``.
+
+        ``ema_decay`` (None or 0: off; otherwise 0 < ema_decay < 1): an exponential moving average of the weights, kept in one more
+        flat buffer by the SAME launch that updates them (csrc/adam_ema.hip): e <- e + (1 - d) (w' - e), with d = ema_decay, or
+        with ``ema_warmup`` d = min(ema_decay, (1 + t) / (10 + t)) at the step count t of the launch.  The average starts at the
+        initial (or loaded) weights.  The weights, moments and step counts are bit for bit those of the optimizer without it.  A
+        step the guard skips leaves the average alone, and under ``device_step`` the schedule follows the device-side count, so a
+        captured iteration keeps averaging.  On the host-count path a parameter WITHOUT a gradient in some iteration keeps its
+        average as well as its weight: the weight did not move, and the average is not pulled further towards it.  Under
+        ``device_step`` a parameter that never has a gradient rides along: w' == w keeps its average at w up to rounding.  The
+        average is element-wise over the flat buffer: data-parallel ranks hold the same one without communication.
+        ``ema_buffer()``, ``ema_state_dict(module)`` and ``swap_ema()`` read and use it."""
         defaults = dict(lr=lr, betas=(float(betas[0]), float(betas[1])), eps=eps, weight_decay=weight_decay)
         super().__init__(params, defaults)
         self.grad_sync = grad_sync
@@ -72,6 +84,11 @@ class Adam(torch.optim.Optimizer):
             raise ops.HrvError("Adam: skip_nonfinite=True needs the step count on the device; build the optimizer with "
                                "device_step=True")
         self.guarded = self.max_grad_norm is not None or self.skip_nonfinite
+        self.ema_decay = float(ema_decay) if ema_decay else None
+        if self.ema_decay is not None and not 0.0 < self.ema_decay < 1.0:
+            raise ops.HrvError(f"Adam: ema_decay must lie strictly between 0 and 1 (None or 0 switches the average off), got {ema_decay}")
+        self.ema_warmup = bool(ema_warmup)
+        self._swapped = False
 
     @property
     def guard_record(self):
@@ -121,6 +138,8 @@ class Adam(torch.optim.Optimizer):
         # in some iteration (skipped below) falls behind the others, and its bias correction must use ITS count
         st = dict(w=w, m=torch.zeros_like(w), v=torch.zeros_like(w), g=torch.zeros_like(w), spans=spans, step=0,
                   steps=[0] * len(spans))
+        if self.ema_decay is not None:
+            st["ema"] = w.clone()
         if self.guarded:      # record + workspace exist before any step (a captured step() allocates nothing)
             st["guard"], st["guard_part"], st["guard_cnt"] = T.guard_alloc(dev)
         self._flat[gi] = st
@@ -151,6 +170,8 @@ class Adam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():            # like torch.optim: the closure may call backward()
                 loss = closure()
+        if self._swapped:
+            raise ops.HrvError("Adam.step() inside swap_ema(): the flat weight buffer holds the averaged weights; leave the context first")
         from . import train_ops as _T
         _T.wgrad_join()            # weight gradients of the last backward may sit on the side stream (train_ops.wgrad_side)
         world_scale = 1.0
@@ -178,7 +199,7 @@ class Adam(torch.optim.Optimizer):
                         st.setdefault("never", set()).add(i)
                         continue
                     skipped.append((off, k, st["w"][off:off + k].clone(), st["m"][off:off + k].clone(),
-                                    st["v"][off:off + k].clone()))
+                                    st["v"][off:off + k].clone(), st["ema"][off:off + k].clone() if "ema" in st else None))
                 else:
                     if self.device_step and i in st.get("never", ()):      # ... and one that rode along cannot join later
                         missing += 1
@@ -187,6 +208,7 @@ class Adam(torch.optim.Optimizer):
                         g[off:off + k].copy_(src.reshape(-1))
             st["step"] += 1
             b1, b2 = group["betas"]
+            ema, decay, warm = st.get("ema"), self.ema_decay, self.ema_warmup
             if self.guarded:
                 # the padding between spans is zero (zeros_like; every writer takes a k-element view): the sum over the buffer
                 # is the sum over the parameters' elements
@@ -205,8 +227,15 @@ class Adam(torch.optim.Optimizer):
                 if self.guarded:
                     T.grad_guard_finalize(st["guard_part"], st["guard_cnt"], st["guard"], world_scale, self.max_grad_norm,
                                           self.skip_nonfinite, st["step_dev"], st["lr_dev"], st["hyper"], b1, b2)
-                    T.adam_step_dev_guarded(st["w"], g, st["m"], st["v"], st["hyper"], b1, b2, group["eps"], group["weight_decay"],
-                                            world_scale, st["guard"])
+                    if ema is not None:
+                        T.adam_step_dev_guarded_ema(st["w"], g, st["m"], st["v"], ema, st["hyper"], b1, b2, group["eps"],
+                                                    group["weight_decay"], world_scale, st["guard"], st["step_dev"], decay, warm)
+                    else:
+                        T.adam_step_dev_guarded(st["w"], g, st["m"], st["v"], st["hyper"], b1, b2, group["eps"], group["weight_decay"],
+                                                world_scale, st["guard"])
+                elif ema is not None:
+                    T.adam_step_dev_ema(st["w"], g, st["m"], st["v"], ema, st["step_dev"], st["lr_dev"], st["hyper"], b1, b2, group["eps"],
+                                        group["weight_decay"], world_scale, decay, warm)
                 else:
                     T.adam_step_dev(st["w"], g, st["m"], st["v"], st["step_dev"], st["lr_dev"], st["hyper"], b1, b2, group["eps"],
                                     group["weight_decay"], world_scale)
@@ -216,7 +245,7 @@ class Adam(torch.optim.Optimizer):
             # one launch per run of consecutive spans that share a step count (a skipped span rides along with either
             # neighbour: it is restored afterwards) -- ONE launch over the whole buffer unless some parameter fell behind
             runs, n_sp = [], len(st["spans"])
-            skipped_offs = {off for off, _, _, _, _ in skipped}
+            skipped_offs = {s[0] for s in skipped}
             i = 0
             while i < n_sp:
                 if st["spans"][i][1] in skipped_offs:
@@ -232,21 +261,96 @@ class Adam(torch.optim.Optimizer):
             if len(runs) == 1 and len(skipped) == 0:
                 runs = [(0, g.numel(), runs[0][2])]
             for a, b, cnt in runs:
-                if self.guarded:
+                if ema is not None and self.guarded:
+                    T.adam_step_guarded_ema(st["w"][a:b], g[a:b], st["m"][a:b], st["v"][a:b], ema[a:b], float(group["lr"]), b1, b2,
+                                            group["eps"], group["weight_decay"], cnt, world_scale, st["guard"], decay, warm)
+                elif ema is not None:
+                    T.adam_step_ema(st["w"][a:b], g[a:b], st["m"][a:b], st["v"][a:b], ema[a:b], float(group["lr"]), b1, b2, group["eps"],
+                                    group["weight_decay"], cnt, world_scale, decay, warm)
+                elif self.guarded:
                     T.adam_step_guarded(st["w"][a:b], g[a:b], st["m"][a:b], st["v"][a:b], float(group["lr"]), b1, b2, group["eps"],
                                         group["weight_decay"], cnt, world_scale, st["guard"])
                 else:
                     T.adam_step(st["w"][a:b], g[a:b], st["m"][a:b], st["v"][a:b], float(group["lr"]), b1, b2, group["eps"],
                                 group["weight_decay"], cnt, world_scale)
-            for off, k, w0, m0, v0 in skipped:
+            for off, k, w0, m0, v0, e0 in skipped:
                 st["w"][off:off + k].copy_(w0)
                 st["m"][off:off + k].copy_(m0)
                 st["v"][off:off + k].copy_(v0)
+                if e0 is not None:
+                    st["ema"][off:off + k].copy_(e0)
+        self._bump_epochs()
+        return loss
+
+    def _bump_epochs(self):
         for group in self.param_groups:          # cached inference plans of THESE parameters are stale now
             for p in group["params"]:
                 p._hrv_epoch = getattr(p, "_hrv_epoch", 0) + 1
         ops.WEIGHTS_EPOCH[0] += 1
-        return loss
+
+    # ------------------------------------------------------------------ the averaged weights
+    def _ema_state(self, gi, what):
+        if self.ema_decay is None:
+            raise ops.HrvError(f"Adam.{what}: the optimizer was built without ema_decay")
+        return self._flat.get(gi) or self._setup(gi, self.param_groups[gi])
+
+    def ema_buffer(self, group: int = 0):
+        """The flat fp32 buffer of averaged weights of one parameter group, laid out like the flat weight buffer."""
+        return self._ema_state(group, "ema_buffer")["ema"]
+
+    def ema_state_dict(self, module):
+        """``module.state_dict()`` with every parameter this optimizer owns replaced by (a copy of) its averaged value; the keys
+        are the module's, so the file loads wherever the raw checkpoint does.  Buffers stay the live ones -- spectral norm's
+        ``weight_u`` / ``weight_v``, BatchNorm statistics: they are no parameters and are not averaged, the usual practice."""
+        where = {}
+        for gi in range(len(self.param_groups)):
+            st = self._ema_state(gi, "ema_state_dict")
+            for p, off, k in st["spans"]:
+                where[id(p)] = (st["ema"], off, k)
+        sd = module.state_dict()
+        for name, p in module.named_parameters():
+            if id(p) in where and name in sd:
+                e, off, k = where[id(p)]
+                sd[name] = e[off:off + k].view_as(p).clone()
+        return sd
+
+    def load_ema_state_dict(self, module, sd):
+        """Seed the average from a file ema_state_dict() produced: every parameter of ``module`` this optimizer owns whose key is
+        in ``sd`` takes that value; the others keep theirs."""
+        where = {}
+        for gi in range(len(self.param_groups)):
+            st = self._ema_state(gi, "load_ema_state_dict")
+            for p, off, k in st["spans"]:
+                where[id(p)] = (st["ema"], off, k)
+        for name, p in module.named_parameters():
+            if id(p) in where and name in sd:
+                e, off, k = where[id(p)]
+                if sd[name].numel() != k:
+                    raise ops.HrvError(f"load_ema_state_dict: {name} has {sd[name].numel()} elements, the parameter {k}")
+                e[off:off + k].copy_(sd[name].reshape(-1).to(e.device, torch.float32))
+
+    @contextlib.contextmanager
+    def swap_ema(self):
+        """Inside the context the parameters HOLD the averaged weights (the flat weight and average buffers are exchanged in place
+        by hrv_swap_f32, per group, on entry and again on exit: no clone of the buffer), for evaluation.  Cached inference plans
+        rebuild (ops.WEIGHTS_EPOCH and every parameter's ``_hrv_epoch`` move both times).  Not exchanged: buffers (spectral
+        norm's ``u`` / ``v``); a hipGraph captured before still works on the same addresses and would read the averaged weights
+        while inside.  step() raises inside the context."""
+        if self._swapped:
+            raise ops.HrvError("Adam.swap_ema(): already inside swap_ema()")
+        states = [self._ema_state(gi, "swap_ema") for gi in range(len(self.param_groups))]
+
+        def exchange():
+            for st in states:
+                T.swap_(st["w"], st["ema"])
+            self._bump_epochs()
+        exchange()
+        self._swapped = True
+        try:
+            yield self
+        finally:
+            exchange()
+            self._swapped = False
 
     # ------------------------------------------------------------------ (de)serialisation
     def state_dict(self):
@@ -267,6 +371,8 @@ class Adam(torch.optim.Optimizer):
                     state[idx] = {"step": torch.tensor(float(stp)),
                                   "exp_avg": st["m"][off:off + k].view_as(p).clone(),
                                   "exp_avg_sq": st["v"][off:off + k].view_as(p).clone()}
+                    if "ema" in st:
+                        state[idx]["ema"] = st["ema"][off:off + k].view_as(p).clone()
                 ids.append(idx)
                 idx += 1
             g = {k: v for k, v in group.items() if k != "params"}
@@ -284,10 +390,14 @@ class Adam(torch.optim.Optimizer):
             spans = {id(p): (off, k) for p, off, k in st["spans"]}
             pos = {id(p): i for i, (p, _, _) in enumerate(st["spans"])}
             loaded = None
+            if "ema" in st:      # a state without "ema" (saved with the average off): the average starts at the weights
+                st["ema"].copy_(st["w"])
             for p in group["params"]:
                 ent = sd["state"].get(idx)
                 if ent is not None and id(p) in spans:
                     off, k = spans[id(p)]
+                    if "ema" in st and "ema" in ent:
+                        st["ema"][off:off + k].copy_(ent["ema"].reshape(-1).to(st["ema"].device))
                     st["m"][off:off + k].copy_(ent["exp_avg"].reshape(-1).to(st["m"].device))
                     st["v"][off:off + k].copy_(ent["exp_avg_sq"].reshape(-1).to(st["v"].device))
                     st["steps"][pos[id(p)]] = int(ent["step"])
@@ -327,6 +437,29 @@ def guard_kwargs(opt, which):
     if getattr(opt, "skip_nonfinite", False):
         kw.update(skip_nonfinite=True, device_step=True)
     return kw
+
+
+def add_ema_args(parser):
+    """--ema_decay / --ema_warmup / --ema_eval / --ema_checkpoint of train_generator.py (the generator's optimizer only).  Like the
+    guard's flags they appear in the parsed namespace only when given."""
+    import argparse
+    parser.add_argument("--ema_decay", type=float, default=argparse.SUPPRESS,
+                        help="keep an exponential moving average of the generator's weights with this decay, inside the fused Adam "
+                             "launch (0: off); gen_ema_step_*.pth / gen_ema_model_final.pth are written beside the raw checkpoints")
+    parser.add_argument("--ema_warmup", action="store_true", default=argparse.SUPPRESS,
+                        help="decay min(ema_decay, (1 + t) / (10 + t)) at optimizer step t")
+    parser.add_argument("--ema_eval", action="store_true", default=argparse.SUPPRESS,
+                        help="run the test/LPIPS pass and the test_images grids with the averaged weights")
+    parser.add_argument("--ema_checkpoint", type=str, default=argparse.SUPPRESS,
+                        help="a gen_ema_*.pth file that seeds the average of a resumed run")
+
+
+def ema_kwargs(opt):
+    """Adam's keyword arguments for the generator's optimizer; empty (the plain construction) without --ema_decay."""
+    decay = float(getattr(opt, "ema_decay", 0.0) or 0.0)
+    if decay == 0.0:
+        return {}
+    return dict(ema_decay=decay, ema_warmup=bool(getattr(opt, "ema_warmup", False)))
 
 
 def guard_scalars(opt_g, opt_d):

@@ -954,6 +954,77 @@ def adam_step_dev_guarded(w: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: 
                    "hrv_adam_dev_guarded_f32")
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# Adam step that also keeps an exponential moving average of the weights (csrc/adam_ema.hip; contract: include/hrviton_hip.h).
+# Each mirrors the step of the same name above and writes the same w, m, v bit for bit; ``ema`` is one more flat fp32 buffer
+# (read and written once: 36 bytes per element), ``decay`` in [0, 1), ``warmup``: d = min(decay, (1 + t) / (10 + t)).
+# ---------------------------------------------------------------------------------------------------------------
+def _ema_args(w: torch.Tensor, ema: torch.Tensor, decay: float):
+    ops.require_cuda(ema, "adam_step_ema(ema)")
+    if ema.dtype != torch.float32 or not ema.is_contiguous() or ema.numel() != w.numel():
+        raise ops.HrvError("adam_step_ema: ema is a contiguous fp32 buffer of the weights' length")
+    if not 0.0 <= float(decay) < 1.0:
+        raise ops.HrvError(f"adam_step_ema: decay must lie in [0, 1), got {decay}")
+
+
+def adam_step_ema(w: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, ema: torch.Tensor, lr: float, beta1: float,
+                  beta2: float, eps: float, weight_decay: float, step: int, grad_scale: float, decay: float, warmup: bool = False):
+    lib = _lib.load()
+    _ema_args(w, ema, decay)
+    with _Timed("adam", "adam_ema_f32", 0.0, 36.0 * w.numel()):     # read w, g, m, v, ema; write w, m, v, ema
+        _lib.check(lib.hrv_adam_ema_f32(w.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ema.data_ptr(), w.numel(), lr, beta1, beta2,
+                                        eps, weight_decay, step, grad_scale, decay, int(bool(warmup)), _stream()), "hrv_adam_ema_f32")
+
+
+def adam_step_dev_ema(w: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, ema: torch.Tensor, step_dev: torch.Tensor,
+                      lr_dev: torch.Tensor, hyper: torch.Tensor, beta1: float, beta2: float, eps: float, weight_decay: float,
+                      grad_scale: float, decay: float, warmup: bool = False):
+    """adam_step_dev + the average: hrv_adam_hyper_f32 advances the count, the launch reads it for the warm-up schedule."""
+    lib = _lib.load()
+    _ema_args(w, ema, decay)
+    _lib.check(lib.hrv_adam_hyper_f32(step_dev.data_ptr(), lr_dev.data_ptr(), beta1, beta2, hyper.data_ptr(), _stream()),
+               "hrv_adam_hyper_f32")
+    with _Timed("adam", "adam_ema_f32", 0.0, 36.0 * w.numel()):
+        _lib.check(lib.hrv_adam_dev_ema_f32(w.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ema.data_ptr(), w.numel(),
+                                            hyper.data_ptr(), beta1, beta2, eps, weight_decay, grad_scale, decay, int(bool(warmup)),
+                                            step_dev.data_ptr(), _stream()), "hrv_adam_dev_ema_f32")
+
+
+def adam_step_guarded_ema(w: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, ema: torch.Tensor, lr: float, beta1: float,
+                          beta2: float, eps: float, weight_decay: float, step: int, grad_scale: float, record: torch.Tensor, decay: float,
+                          warmup: bool = False):
+    lib = _lib.load()
+    _ema_args(w, ema, decay)
+    with _Timed("adam", "adam_ema_f32", 0.0, 36.0 * w.numel()):
+        _lib.check(lib.hrv_adam_guarded_ema_f32(w.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ema.data_ptr(), w.numel(), lr, beta1,
+                                                beta2, eps, weight_decay, step, grad_scale, record.data_ptr(), decay, int(bool(warmup)),
+                                                _stream()), "hrv_adam_guarded_ema_f32")
+
+
+def adam_step_dev_guarded_ema(w: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, ema: torch.Tensor, hyper: torch.Tensor,
+                              beta1: float, beta2: float, eps: float, weight_decay: float, grad_scale: float, record: torch.Tensor,
+                              step_dev: torch.Tensor, decay: float, warmup: bool = False):
+    """The device-step launch alone (grad_guard_finalize with step_dev / lr_dev / hyper has already counted an applied step)."""
+    lib = _lib.load()
+    _ema_args(w, ema, decay)
+    with _Timed("adam", "adam_ema_f32", 0.0, 36.0 * w.numel()):
+        _lib.check(lib.hrv_adam_dev_guarded_ema_f32(w.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ema.data_ptr(), w.numel(),
+                                                    hyper.data_ptr(), beta1, beta2, eps, weight_decay, grad_scale, record.data_ptr(), decay,
+                                                    int(bool(warmup)), step_dev.data_ptr(), _stream()), "hrv_adam_dev_guarded_ema_f32")
+
+
+def swap_(a: torch.Tensor, b: torch.Tensor):
+    """Exchange two flat fp32 buffers in place, one pass, no temporary (hrv_swap_f32)."""
+    lib = _lib.load()
+    ops.require_cuda(a, "swap_(a)")
+    ops.require_cuda(b, "swap_(b)")
+    if a.dtype != torch.float32 or b.dtype != torch.float32 or not a.is_contiguous() or not b.is_contiguous() or a.numel() != b.numel() \
+            or a.numel() < 1:
+        raise ops.HrvError("swap_: two non-empty contiguous fp32 buffers of one length are required")
+    with _Timed("ew", "swap_f32", 0.0, 16.0 * a.numel()):
+        _lib.check(lib.hrv_swap_f32(a.data_ptr(), b.data_ptr(), a.numel(), _stream()), "hrv_swap_f32")
+
+
 def spectral_sigma(w_orig: torch.Tensor, u: torch.Tensor, v: torch.Tensor, power_iterations: int,
                    eps: float = 1e-12) -> torch.Tensor:
     """In-place power iteration on (u, v) + sigma (device scalar tensor [1])."""

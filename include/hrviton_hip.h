@@ -451,6 +451,30 @@ int hrv_adam_guarded_f32(float* w, const float* g, float* m, float* v, int64_t n
 int hrv_adam_dev_guarded_f32(float* w, const float* g, float* m, float* v, int64_t n, const float* hyper_dev, float beta1,
                              float beta2, float eps, float weight_decay, float grad_scale, const int32_t* record,
                              hrv_stream_t stream);
+/* The four Adam launches above, each also keeping an exponential moving average ``ema`` of the weights (one more buffer of n
+ * floats, read and written once: 36 bytes per element).  Per element, in fp32:
+ *   w', m', v' = what the launch of the same name without _ema writes for the same arguments, bit for bit
+ *   d   = warmup ? fminf(decay, (1 + t) / (10 + t)) : decay      t = the step count of this launch, as float
+ *   omd = 1.f - d
+ *   e'  = omd == 1.f ? w' : fmaf(omd, w' - e, e)                  (w' - e rounded to fp32 first)
+ * 0 <= decay < 1.  t is ``step`` in the host-count variants; the device-count variants read step_dev[0], which hrv_adam_hyper_f32 /
+ * hrv_grad_guard_finalize_hyper have already advanced for an applied step.  A guarded launch with apply == 0 leaves ema alone, like
+ * w, m and v.  Any n >= 1 and any 4-byte-aligned pointers; with all five pointers on 16-byte boundaries a thread moves 16 bytes of
+ * each array per trip, otherwise the whole launch moves 4.
+ * hrv_swap_f32 exchanges a[0, n) and b[0, n) in place in one pass, no temporary (the buffers must not overlap); the same
+ * alignment rule. */
+int hrv_adam_ema_f32(float* w, const float* g, float* m, float* v, float* ema, int64_t n, float lr, float beta1, float beta2,
+                     float eps, float weight_decay, int32_t step, float grad_scale, float decay, int32_t warmup, hrv_stream_t stream);
+int hrv_adam_dev_ema_f32(float* w, const float* g, float* m, float* v, float* ema, int64_t n, const float* hyper_dev, float beta1,
+                         float beta2, float eps, float weight_decay, float grad_scale, float decay, int32_t warmup,
+                         const int32_t* step_dev, hrv_stream_t stream);
+int hrv_adam_guarded_ema_f32(float* w, const float* g, float* m, float* v, float* ema, int64_t n, float lr, float beta1, float beta2,
+                             float eps, float weight_decay, int32_t step, float grad_scale, const int32_t* record, float decay,
+                             int32_t warmup, hrv_stream_t stream);
+int hrv_adam_dev_guarded_ema_f32(float* w, const float* g, float* m, float* v, float* ema, int64_t n, const float* hyper_dev,
+                                 float beta1, float beta2, float eps, float weight_decay, float grad_scale, const int32_t* record,
+                                 float decay, int32_t warmup, const int32_t* step_dev, hrv_stream_t stream);
+int hrv_swap_f32(float* a, float* b, int64_t n, hrv_stream_t stream);
 /* torch spectral_norm (SpectralNorm.compute_weight): `power_iterations` rounds of
  * v<-normalize(W^T u), u<-normalize(W v) in place (eps 1e-12), then sigma = u.(W v).
  * W is [R][K] = weight_orig.reshape(Cout,-1); wv_scratch holds R floats.

@@ -28,6 +28,7 @@ Bug-fixes of the reference call sites: tocg(input1, input2) arity, 
 Adam betas as floats.
 """
 import argparse
+import contextlib
 import os
 import sys
 import time
@@ -47,7 +48,7 @@ from hr_viton_amd.gen_train import attach_grad_sync  # noqa: E402
 from hr_viton_amd.losses import GANLoss, L1Loss  # noqa: E402
 from hr_viton_amd.network_generator import MultiscaleDiscriminator, SPADEGenerator  # noqa: E402
 from hr_viton_amd.networks import ConditionGenerator  # noqa: E402
-from hr_viton_amd.optim import Adam, add_guard_args, guard_kwargs, guard_line, guard_scalars  # noqa: E402
+from hr_viton_amd.optim import Adam, add_ema_args, add_guard_args, ema_kwargs, guard_kwargs, guard_line, guard_scalars  # noqa: E402
 from hr_viton_amd.parallel import broadcast_module  # noqa: E402
 from hr_viton_amd.pipeline import generator_train_step, make_generator_inputs  # noqa: E402
 from hr_viton_amd.validate import (generator_validation_lpips, load_validation_lpips, val_items_loader,  # noqa: E402
@@ -130,6 +131,7 @@ def get_opt(argv=None):
     p.add_argument("--board", action="store_true",
                    help="every --tensorboard_count steps record the loss scalars and the image grids (train_generator.py:364-478)")
     add_guard_args(p)
+    add_ema_args(p)
     opt = p.parse_args(argv)
     opt.gpu_ids = [int(s) for s in str(opt.gpu_ids).split(",") if s.strip() and int(s) >= 0]
     return opt
@@ -167,6 +169,11 @@ class _Validation(object):
         self.board = viz.BoardLog(os.path.join(opt.tensorboard_dir, opt.name))
         self.vis = None
         self.opt_g = self.opt_d = None      # the optimizers whose guard records ride along with the loss scalars (main sets them)
+        self.ema_eval = False               # --ema_eval: the test passes run on opt_g's averaged weights (main sets it)
+
+    def weights(self):
+        """The context the test passes run in: the generator's averaged weights with --ema_eval, the raw ones otherwise."""
+        return self.opt_g.swap_ema() if self.ema_eval else contextlib.nullcontext()
 
     def vis_batch(self):
         """The test-visualisation batch (:383-395): the first --num_test_visualize test items with the unpaired cloth, loaded once."""
@@ -197,8 +204,9 @@ class _Validation(object):
             self.board.add_scalar(tag, val, s)
         if opt.num_test_visualize > 0:
             vb = self.vis_batch()
-            fields, out = viz.generator_fields(opt, tocg, generator, vb)
-            grids = viz.to_host(viz.generator_train_grid(vb, fields, out, quant=viz.TRUNC))
+            with self.weights():
+                fields, out = viz.generator_fields(opt, tocg, generator, vb)
+                grids = viz.to_host(viz.generator_train_grid(vb, fields, out, quant=viz.TRUNC))
             for i in range(grids.shape[0]):
                 self.board.add_image("test_images/%d" % i, grids[i], s)
 
@@ -220,7 +228,8 @@ class _Validation(object):
         if self.model is None:
             return None
         print("LPIPS")
-        res = generator_validation_lpips(self.opt, tocg, generator, self.model, self.batches(), max_items=self.opt.val_items)
+        with self.weights():
+            res = generator_validation_lpips(self.opt, tocg, generator, self.model, self.batches(), max_items=self.opt.val_items)
         if res["items"]:
             avg_distance = res["lpips"]
             print(f"LPIPS{avg_distance}")
@@ -279,7 +288,12 @@ def main(argv=None):
         crit_vgg.to(dev)
         broadcast_module(crit_vgg)
 
-    opt_g = Adam(generator.parameters(), lr=opt.G_lr, betas=(0.0, 0.9), **guard_kwargs(opt, "G"))
+    ema = ema_kwargs(opt)      # (empty without --ema_decay: the plain construction, nothing allocated)
+    if not ema and (getattr(opt, "ema_eval", False) or getattr(opt, "ema_checkpoint", "")):
+        raise SystemExit("--ema_eval / --ema_checkpoint need --ema_decay")
+    opt_g = Adam(generator.parameters(), lr=opt.G_lr, betas=(0.0, 0.9), **guard_kwargs(opt, "G"), **ema)
+    if ema and getattr(opt, "ema_checkpoint", ""):
+        opt_g.load_ema_state_dict(generator, torch.load(opt.ema_checkpoint, map_location="cpu"))
     opt_d = Adam(discriminator.parameters(), lr=opt.D_lr, betas=(0.0, 0.9), **guard_kwargs(opt, "D"))
     # in-place bucketed all-reduce on the optimizers' flat gradient buffers, fired from inside the backward
     sync_g = opt_g.make_grad_sync() if world > 1 else None
@@ -305,6 +319,7 @@ def main(argv=None):
     validation = _Validation(opt, dev) if rank == 0 else None
     if validation is not None:
         validation.opt_g, validation.opt_d = opt_g, opt_d
+        validation.ema_eval = bool(ema) and bool(getattr(opt, "ema_eval", False))
     for step in range(opt.load_step, last):
         t0 = time.time()
         if loader is None:
@@ -331,12 +346,18 @@ def main(argv=None):
         if (step + 1) % opt.save_count == 0 and rank == 0:
             save_checkpoint(generator, os.path.join(opt.checkpoint_dir, opt.name, "gen_step_%06d.pth" % (step + 1)), opt)
             save_checkpoint(discriminator, os.path.join(opt.checkpoint_dir, opt.name, "dis_step_%06d.pth" % (step + 1)), opt)
+            if ema:
+                save_checkpoint(generator, os.path.join(opt.checkpoint_dir, opt.name, "gen_ema_step_%06d.pth" % (step + 1)), opt,
+                                state_dict=opt_g.ema_state_dict(generator))
         if (step + 1) % 1000 == 0:
             sched_g.step()
             sched_d.step()
     if rank == 0:
         save_checkpoint(generator, os.path.join(opt.checkpoint_dir, opt.name, "gen_model_final.pth"), opt)
         save_checkpoint(discriminator, os.path.join(opt.checkpoint_dir, opt.name, "dis_model_final.pth"), opt)
+        if ema:
+            save_checkpoint(generator, os.path.join(opt.checkpoint_dir, opt.name, "gen_ema_model_final.pth"), opt,
+                            state_dict=opt_g.ema_state_dict(generator))
         validation.board.close()
         print("Finished training %s!" % opt.name)
 
