@@ -178,6 +178,8 @@ class hrv_lpips_tap_t(C.Structure):
 HRV_VIZ_MAX_PANELS, HRV_VIZ_MAX_CLASSES = 16, 20
 VIZ_SIGNED, VIZ_UNIT, VIZ_SEGMAP = 0, 1, 2      # hrv_viz_panel_t.kind
 VIZ_ROUND, VIZ_TRUNC = 0, 1                     # hrv_viz_grid_u8's quant
+DIFFAUG_COLOR, DIFFAUG_TRANSLATION, DIFFAUG_CUTOUT = 1, 2, 4      # the policy bits of hrv_diffaug_*
+DIFFAUG_SLOTS = 128                             # HRV_DIFFAUG_SLOTS: fp64 partials per sample of hrv_diffaug_mean_f32 / _gsum_f32
 
 
 class hrv_viz_panel_t(C.Structure):
@@ -295,6 +297,10 @@ SYMBOLS = {
     "hrv_conv_cout1_wgrad_slabs": (_i32, [_i32, _i32, _i32]),
     "hrv_conv_cout1_wgrad_f32": (C.c_int, [C.POINTER(hrv_conv_cout1_t), _vp, _i32, _vp, _i32, _vp]),
     "hrv_concat_nhwc_nchw_f32": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
+    "hrv_diffaug_mean_f32": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "hrv_diffaug_concat_f32": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
+    "hrv_diffaug_gsum_f32": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "hrv_diffaug_bwd_f32": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "hrv_resize_bilinear_nhwc_f32": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f, _f,
                                                _vp, _i32, _i32, _vp, _i32, _i32, _vp]),
     "hrv_flow_warp_nhwc_f32": (C.c_int, [C.POINTER(hrv_flow_warp_t), _vp]),

@@ -17,7 +17,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import _lib, ops
 from . import train_ops as T
 from .ops import ACT_LRELU, ACT_NONE, ACT_RELU, ACT_TANH, Act, _ceil4
 
@@ -1357,16 +1357,27 @@ class _DiscPairFn(torch.autograd.Function):
     """The [fake ; real] discriminator pass of train_generator.py:283-295 / :327-345 without the three torch.cat's and the
     layout round trip: the PatchGAN input cat((parse, image), 1) of both halves is assembled NHWC by one kernel per half
     (hrv_concat_nhwc_nchw_f32) straight from the label-map activation and the two NCHW images, and the backward returns
-    d(fake image) only -- the label map and the real image have no gradient.  Same outputs as _DiscFn with ``split``."""
+    d(fake image) only -- the label map and the real image have no gradient.  Same outputs as _DiscFn with ``split``.
+
+    ``aug``: None, or (policy bits, u [N,8]) -- DiffAugment (diffaug.py): the two assembly launches and the extraction of d(fake)
+    are replaced by their augmenting twins (csrc/diffaug.hip), both halves under the same uniforms; with color, one launch
+    for the image means of both halves in front and one for the gradient sums behind."""
 
     @staticmethod
-    def forward(ctx, msd, plan, parse7, fake, real, *params):
+    def forward(ctx, msd, plan, parse7, fake, real, aug, *params):
         N, Cb, H, W = fake.shape
         assert tuple(real.shape) == tuple(fake.shape) and (parse7.N, parse7.H, parse7.W) == (N, H, W) and not parse7.bf16
         Ca = parse7.C
         a = Act(torch.empty((2 * N, H, W, _ceil4(Ca + Cb)), dtype=torch.float32, device=fake.device), Ca + Cb)
-        T.concat_nhwc_nchw(parse7, fake.detach(), Act(a.t[:N], Ca + Cb))
-        T.concat_nhwc_nchw(parse7, real.detach(), Act(a.t[N:], Ca + Cb))
+        if aug is None:
+            T.concat_nhwc_nchw(parse7, fake.detach(), Act(a.t[:N], Ca + Cb))
+            T.concat_nhwc_nchw(parse7, real.detach(), Act(a.t[N:], Ca + Cb))
+        else:
+            flags, u = aug
+            mean = T.diffaug_mean(fake.detach(), real.detach()) if flags & _lib.DIFFAUG_COLOR else None
+            T.diffaug_concat(parse7, fake.detach(), u, None if mean is None else mean[:N], flags, Act(a.t[:N], Ca + Cb))
+            T.diffaug_concat(parse7, real.detach(), u, None if mean is None else mean[N:], flags, Act(a.t[N:], Ca + Cb))
+        ctx.aug = aug
         feats_all, saved = plan.forward(None, power_iteration=True, a=a)
         ctx.plan, ctx.saved, ctx.params, ctx.split = plan, saved, params, True
         ctx.set_materialize_grads(False)
@@ -1381,21 +1392,34 @@ class _DiscPairFn(torch.autograd.Function):
         T.wgrad_join()
         N, Ca, Cb = ctx.cut
         d_fake = None
-        if d_in is not None:
+        if d_in is not None and ctx.aug is None:
             d_fake = ops.to_nchw(Act(d_in.t[:N], Ca + Cb), Ca, Cb)      # channels [Ca, Ca+Cb) of the fake half
-        return (None, None, None, d_fake, None) + tuple(grads.get(p) for p in ctx.params)
+        elif d_in is not None:      # the adjoint of the augmented assembly of the fake half
+            flags, u = ctx.aug
+            g = Act(d_in.t[:N], Ca + Cb)
+            d_fake = T.diffaug_bwd(g, Ca, u, T.diffaug_gsum(g, Ca, u, flags) if flags & _lib.DIFFAUG_COLOR else None, flags)
+        return (None, None, None, d_fake, None, None) + tuple(grads.get(p) for p in ctx.params)
 
 
-def discriminator_train_forward_pair(msd: nn.Module, parse7: Act, fake: torch.Tensor, real: torch.Tensor):
+def discriminator_train_forward_pair(msd: nn.Module, parse7: Act, fake: torch.Tensor, real: torch.Tensor, aug=None, aug_u=None):
     """discriminator(cat((cat((parse, fake), 1), cat((parse, real), 1)), 0)) of train_generator.py:283-295, returning
-    (pred_fake, pred_real) like ``discriminator_train_forward(..., split=True)`` -- see _DiscPairFn."""
+    (pred_fake, pred_real) like ``discriminator_train_forward(..., split=True)`` -- see _DiscPairFn.  ``aug``: a
+    diffaug.DiffAugment (default None: the plain assembly, no other launch); ``aug_u``: its uniforms [N,8] (default: drawn here)."""
     ops.require_cuda(fake, "MultiscaleDiscriminator.forward_pair")
+    if aug is None and aug_u is not None:
+        raise _lib.HrvError("forward_pair: aug_u without aug")
+    if aug is not None:
+        from .diffaug import check_u
+        N = fake.shape[0]
+        if parse7.cstride != 8 or parse7.coff != 0 or fake.shape[1] != 3:
+            raise _lib.HrvError("forward_pair: DiffAugment serves the PatchGAN shape only (parse map with channel stride 8, 3 image channels)")
+        aug = (aug.flags, aug.draw(N, fake.device) if aug_u is None else check_u(aug_u, N, fake.device, "forward_pair"))
     plan = getattr(msd, "_train_plan", None)
     if plan is None:
         plan = msd._train_plan = MultiscaleDTrainPlan(msd)
     params = [p for p in msd.parameters()]
     nD = len(plan.plans)
-    flat = list(_DiscPairFn.apply(msd, plan, parse7, fake, real, *params))     # (under no_grad: no graph is recorded)
+    flat = list(_DiscPairFn.apply(msd, plan, parse7, fake, real, aug, *params))     # (under no_grad: no graph is recorded)
 
     def group(seq):
         per = len(seq) // nD

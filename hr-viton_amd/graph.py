@@ -221,10 +221,11 @@ class GraphedTrainStep:
     the two gradient all-reduces between them, GraphedIteration).  ``inputs``: {'x': [N,9,H,W], 'parse7': the
     label-map activation tensor [N,H,W,8], 'im': [N,3,H,W]} -- static buffers refreshed by ``__call__``.  SPADE noise is
     drawn inside the captured region (torch's graph-safe Philox) unless ``noise`` / ``noise_d`` plane dicts are given
-    (then they are static inputs too).  Losses come back as the static tensors of the capture."""
+    (then they are static inputs too).  ``aug``: a diffaug.DiffAugment; its uniforms are drawn inside the captured region the
+    same way, so every replay augments anew.  Losses come back as the static tensors of the capture."""
 
     def __init__(self, opt, generator, discriminator, crit_gan, crit_feat, crit_vgg, opt_g, opt_d, inputs: Dict[str, torch.Tensor],
-                 noise=None, noise_d=None, warmup: int = 3):
+                 noise=None, noise_d=None, warmup: int = 3, aug=None):
         from .ops import Act
         from .pipeline import generator_train_step
         _lib.load()
@@ -240,7 +241,7 @@ class GraphedTrainStep:
             b = self.static_in
             return generator_train_step(opt, generator, discriminator, crit_gan, crit_feat, crit_vgg, opt_g, opt_d, b["x"],
                                         Act(b["parse7"], 7), b["im"], getattr(opt_g, "grad_sync", None),
-                                        getattr(opt_d, "grad_sync", None), noise=self.noise, noise_d=self.noise_d)
+                                        getattr(opt_d, "grad_sync", None), noise=self.noise, noise_d=self.noise_d, aug=aug)
         self._it = GraphedIteration(body, (opt_g, opt_d), warmup)
         self.graph, self.static_out = self._it.graph, self._it.static_out
         self.replays = 0

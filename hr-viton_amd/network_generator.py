@@ -620,13 +620,15 @@ class MultiscaleDiscriminator(BaseNetwork):
     def downsample(self, input):
         raise RuntimeError("executed inside forward() by hrv_avgpool3x3s2_nhwc_f32")
 
-    def forward_pair(self, parse7, fake, real):
+    def forward_pair(self, parse7, fake, real, aug=None, aug_u=None):
         """Training mode: (pred_fake, pred_real) of discriminator(cat((cat((parse, fake), 1), cat((parse, real), 1)), 0)) --
         train_generator.py:283-295 -- with the input assembled NHWC by one kernel per half instead of three torch.cat's
-        and a layout pass; ``parse7``: the label-map activation (ops.Act), ``fake`` / ``real``: NCHW images."""
+        and a layout pass; ``parse7``: the label-map activation (ops.Act), ``fake`` / ``real``: NCHW images.  ``aug``: a
+        diffaug.DiffAugment -- parse map, fake and real image of a sample are augmented under ONE row of the uniforms ``aug_u``
+        [N,8] (default: drawn on the device), inside the assembly kernels; d(fake) is the transform's adjoint."""
         assert self.training, "forward_pair is the training-step form"
         from .gen_train import discriminator_train_forward_pair
-        return discriminator_train_forward_pair(self, parse7, fake.contiguous(), real.contiguous())
+        return discriminator_train_forward_pair(self, parse7, fake.contiguous(), real.contiguous(), aug=aug, aug_u=aug_u)
 
     def forward(self, input, split: bool = False):
         """List (scales) of lists (layers) of NCHW tensors -- network_generator.py:306-316.  ``split=True`` (an

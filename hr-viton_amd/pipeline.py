@@ -72,12 +72,23 @@ def make_generator_inputs(opt, tocg, inputs: Dict[str, torch.Tensor], aux: Optio
 
 
 def generator_train_step(opt, generator, discriminator, crit_gan, crit_feat, crit_vgg, opt_g, opt_d, x, parse7, im,
-                         sync_g=None, sync_d=None, noise=None, noise_d=None, aux: Optional[dict] = None):
+                         sync_g=None, sync_d=None, noise=None, noise_d=None, aux: Optional[dict] = None, aug=None, aug_u=None):
     """One G step + one D step of train_generator.py:279-360.  ``parse7``: Act [N,H,W,8] (7 real).  ``aux``: a dictionary that
     receives 'output', the D step's generator output, which is what the reference's recording block shows (:368).
     ``noise`` / ``noise_d``: the SPADE noise draws of the two generator forwards (default: drawn like the reference,
-    network_generator.py:104-107); the data-parallel equivalence test injects them."""
+    network_generator.py:104-107); the data-parallel equivalence test injects them.  ``aug``: a diffaug.DiffAugment -- both
+    discriminator calls see their [fake ; real] input augmented (what the VGG term and the caller see is not); ``aug_u`` = (u_G, u_D)
+    injects the uniforms of the generator step's and the discriminator step's call (default: two independent draws on the device)."""
     pair = hasattr(discriminator, "forward_pair") and not getattr(opt, "_hrv_no_pair", False)
+    if aug is None and aug_u is not None:
+        raise ops.HrvError("generator_train_step: aug_u without aug")
+    if aug is not None and not pair:
+        raise ops.HrvError("generator_train_step: DiffAugment lives in the discriminator's pair form (forward_pair); this "
+                           "discriminator / opt._hrv_no_pair takes the concatenated-batch form, which is not augmented")
+    kw_g, kw_d = {}, {}      # (without aug the calls are the ones they always were)
+    if aug is not None:
+        u_g, u_d = aug_u if aug_u is not None else (None, None)
+        kw_g, kw_d = dict(aug=aug, aug_u=u_g), dict(aug=aug, aug_u=u_d)
     parse_nchw = None if pair else ops.to_nchw(parse7)
     # ---------------- generator ----------------
     if sync_g is not None:
@@ -91,7 +102,7 @@ def generator_train_step(opt, generator, discriminator, crit_gan, crit_feat, cri
     discriminator._hrv_discard_param_grads = True      # :354 zeroes D's gradients of loss_gen before they are ever used
     try:
         if pair:      # the same [fake ; real] batch, assembled NHWC inside (no cat / layout round trip)
-            pred_fake, pred_real = discriminator.forward_pair(parse7, output_paired, im)
+            pred_fake, pred_real = discriminator.forward_pair(parse7, output_paired, im, **kw_g)
         else:
             pred_fake, pred_real = discriminator(torch.cat((fake_concat, real_concat), dim=0), split=True)   # :283-295
     finally:
@@ -119,7 +130,7 @@ def generator_train_step(opt, generator, discriminator, crit_gan, crit_feat, cri
     if aux is not None:
         aux["output"] = output
     if pair:
-        pred_fake, pred_real = discriminator.forward_pair(parse7, output, im)
+        pred_fake, pred_real = discriminator.forward_pair(parse7, output, im, **kw_d)
     else:
         fake_concat = torch.cat((parse_nchw, output), dim=1)
         pred_fake, pred_real = discriminator(torch.cat((fake_concat, real_concat), dim=0), split=True)

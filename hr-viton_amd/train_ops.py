@@ -1164,6 +1164,68 @@ def concat_nhwc_nchw(a: Act, b: torch.Tensor, out: Act):
                                                 out.cstride, _stream()), "hrv_concat_nhwc_nchw_f32")
 
 
+# ---- DiffAugment inside the PatchGAN input assembly (csrc/diffaug.hip; the transform is defined in include/hrviton_hip.h) ----
+def _diffaug_part(rows: int, device) -> torch.Tensor:
+    return torch.empty((rows, _lib.DIFFAUG_SLOTS), dtype=torch.float64, device=device)
+
+
+def diffaug_mean(fake: torch.Tensor, real: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Per-sample means of the NCHW images [N,3,H,W] of ``fake`` and then (if given) ``real``: fp32 [N] or [2N], accumulated in
+    fp64 in a fixed order -- hrv_diffaug_mean_f32."""
+    lib = _lib.load()
+    N, Cb, H, W = fake.shape
+    assert Cb == 3 and fake.is_contiguous() and fake.dtype == torch.float32
+    assert real is None or (tuple(real.shape) == tuple(fake.shape) and real.is_contiguous() and real.dtype == torch.float32)
+    rows = N if real is None else 2 * N
+    part, mean = _diffaug_part(rows, fake.device), torch.empty(rows, dtype=torch.float32, device=fake.device)
+    with _Timed("layout", "diffaug_mean", 0.0, 4.0 * rows * 3 * H * W):
+        _lib.check(lib.hrv_diffaug_mean_f32(fake.data_ptr(), None if real is None else real.data_ptr(), N, H, W, part.data_ptr(),
+                                            mean.data_ptr(), _stream()), "hrv_diffaug_mean_f32")
+    return mean
+
+
+def diffaug_concat(a: Act, b: torch.Tensor, u: torch.Tensor, mean: Optional[torch.Tensor], policy: int, out: Act):
+    """The augmenting twin of ``concat_nhwc_nchw``: out = augment(cat((a, b), channels)) under the uniforms ``u`` [N,8] and the
+    per-sample image means ``mean`` [N] (None without color) -- hrv_diffaug_concat_f32."""
+    lib = _lib.load()
+    N, Cb, H, W = b.shape
+    assert (a.N, a.H, a.W) == (N, H, W) == (out.N, out.H, out.W) and not a.bf16 and not out.bf16 and a.coff == 0 and out.coff == 0
+    assert b.is_contiguous() and b.dtype == torch.float32 and out.C == a.C + Cb and out.t.is_contiguous() and a.t.is_contiguous()
+    assert tuple(u.shape) == (N, 8) and u.dtype == torch.float32 and u.is_contiguous()
+    assert mean is None or (mean.numel() == N and mean.dtype == torch.float32 and mean.is_contiguous())
+    if Cb != 3:
+        raise _lib.HrvError(f"diffaug_concat: the image has {Cb} channels; the kernel serves the PatchGAN shape (3)")
+    with _Timed("layout", "diffaug_concat", 0.0, 4.0 * N * H * W * (a.C + Cb + out.cstride)):
+        _lib.check(lib.hrv_diffaug_concat_f32(a.t.data_ptr(), a.C, a.cstride, b.data_ptr(), u.data_ptr(),
+                                              None if mean is None else mean.data_ptr(), policy, N, H, W, out.t.data_ptr(), out.cstride,
+                                              _stream()), "hrv_diffaug_concat_f32")
+
+
+def diffaug_gsum(g: Act, Ca: int, u: torch.Tensor, policy: int) -> torch.Tensor:
+    """fp64 [N]: the selected gradient of the NHWC input gradient ``g`` summed over the destinations and the three image channels
+    [Ca, Ca+3) -- hrv_diffaug_gsum_f32."""
+    lib = _lib.load()
+    assert not g.bf16 and g.coff == 0 and g.t.is_contiguous() and tuple(u.shape) == (g.N, 8) and u.is_contiguous()
+    part, out = _diffaug_part(g.N, g.t.device), torch.empty(g.N, dtype=torch.float64, device=g.t.device)
+    with _Timed("layout", "diffaug_gsum", 0.0, 4.0 * g.N * g.H * g.W * 3):
+        _lib.check(lib.hrv_diffaug_gsum_f32(g.t.data_ptr(), g.cstride, Ca, u.data_ptr(), policy, g.N, g.H, g.W, part.data_ptr(),
+                                            out.data_ptr(), _stream()), "hrv_diffaug_gsum_f32")
+    return out
+
+
+def diffaug_bwd(g: Act, Ca: int, u: torch.Tensor, gsum: Optional[torch.Tensor], policy: int) -> torch.Tensor:
+    """The augmenting twin of ``ops.to_nchw(g, Ca, 3)``: d(image) [N,3,H,W] of the augmented assembly, every element written --
+    hrv_diffaug_bwd_f32."""
+    lib = _lib.load()
+    assert not g.bf16 and g.coff == 0 and g.t.is_contiguous() and tuple(u.shape) == (g.N, 8) and u.is_contiguous()
+    assert gsum is None or (gsum.numel() == g.N and gsum.dtype == torch.float64)
+    out = torch.empty((g.N, 3, g.H, g.W), dtype=torch.float32, device=g.t.device)
+    with _Timed("layout", "diffaug_bwd", 0.0, 4.0 * out.numel() + ops.act_bytes(g, 3)):
+        _lib.check(lib.hrv_diffaug_bwd_f32(g.t.data_ptr(), g.cstride, Ca, u.data_ptr(), None if gsum is None else gsum.data_ptr(),
+                                           policy, g.N, g.H, g.W, out.data_ptr(), _stream()), "hrv_diffaug_bwd_f32")
+    return out
+
+
 def space_to_depth2(a: Act) -> Act:
     """[N,H,W,C] fp32 -> dense [N,H/2,W/2,4*Cp], channel ((y&1)*2 + (x&1))*Cp + c (hrv_space_to_depth2_nhwc_f32)."""
     lib = _lib.load()

@@ -646,6 +646,41 @@ int hrv_conv_cout1_wgrad_f32(const hrv_conv_cout1_t* d, float* dw, int32_t accum
 int hrv_concat_nhwc_nchw_f32(const float* a, int32_t Ca, int32_t a_cstride, int32_t a_coff, const float* b, int32_t Cb, int32_t N,
                              int32_t H, int32_t W, float* out, int32_t out_cstride, hrv_stream_t stream);
 int hrv_depth_to_space2_nhwc_f32(const float* in, int32_t N, int32_t H, int32_t W, int32_t C, float* out, hrv_stream_t stream);
+
+/* ---- DiffAugment (color, translation, cutout) inside the PatchGAN input assembly (diffaug.hip; diffaug.py) ----
+ * The augmenting twins of hrv_concat_nhwc_nchw_f32 and of the hrv_nhwc_to_nchw_f32 slice that extracts d(fake), for the PatchGAN
+ * shape only: a parse map NHWC with channel stride 8 and Ca <= 8 real channels, an image NCHW [N,3,H,W], an output (gradient) NHWC
+ * with channel stride 12; anything else is an argument error.  fp32 storage.  `policy` is a set of HRV_DIFFAUG_* bits; a transform
+ * that is absent takes its identity.  u fp32 [N][8] on the device holds uniforms in [0, 1); row n serves sample n.  Decode, in fp32
+ * with truncation toward zero:
+ *   color        beta = u0 - 0.5,  s = 2 u1,  k = u2 + 0.5
+ *   translation  ty = min((int)(u3 (2 Sy + 1)), 2 Sy) - Sy with Sy = (H + 4) / 8;  tx likewise from u4 and W
+ *   cutout       a box of ch = H / 2 by cw = W / 2: oy = min((int)(u5 (H + 1 - ch % 2)), H - ch % 2), rows oy - ch / 2 <= y <
+ *                oy - ch / 2 + ch; columns likewise from u6 and W; clipped to the image
+ * Forward, destination (y, x) of sample n: the source is (y + ty, x + tx); V = the source lies inside the image and (y, x) lies
+ * outside the box.  V: out[0:Ca] = parse[source], out[Ca + c] = k s x_c + k (1 - s) m + (1 - k) M + beta with x_c the image at the
+ * source, m the mean of its three channels there, M = mean[n] the mean of the whole un-translated image.  Not V: all twelve floats
+ * are 0 -- a select: the source is not read, and the address of a source outside the image is never formed.  Pad channels are 0.
+ * Backward, with G = V ? g : 0 over destinations: d_img[c, y', x'] = k s G_c(dst) + (k (1 - s) / 3) sum_c' G_c'(dst) +
+ * ((1 - k) / (3 H W)) gsum[n], dst = (y' - ty, x' - tx); the first two terms are 0 where dst lies outside the image.  Color is
+ * evaluated in fp64 from the fp32 decode and rounded once; without HRV_DIFFAUG_COLOR both directions copy bits. */
+enum { HRV_DIFFAUG_COLOR = 1, HRV_DIFFAUG_TRANSLATION = 2, HRV_DIFFAUG_CUTOUT = 4 };
+#define HRV_DIFFAUG_SLOTS 128 /* partial sums per sample of the two reductions below */
+/* mean[j] = (float)(sum of sample j in fp64 / (3 H W)) for the N samples of `fake`, then (real != NULL) the N samples of `real`: one
+ * partial pass over both halves and a one-block-per-sample finalisation, fixed order (bit-identical between runs).  part: fp64
+ * [2N][HRV_DIFFAUG_SLOTS] scratch.  A sample's base needs 4-byte alignment only. */
+int hrv_diffaug_mean_f32(const float* fake, const float* real, int32_t N, int32_t H, int32_t W, double* part, float* mean,
+                         hrv_stream_t stream);
+/* a, out 16-byte aligned; mean fp32 [N] (may be NULL without HRV_DIFFAUG_COLOR) */
+int hrv_diffaug_concat_f32(const float* a, int32_t Ca, int32_t a_cstride, const float* b, const float* u, const float* mean,
+                           int32_t policy, int32_t N, int32_t H, int32_t W, float* out, int32_t out_cstride, hrv_stream_t stream);
+/* sum[n] (fp64) = sum of G over the destinations and channels [Ca, Ca + 3) of g NHWC [N,H,W,12]; part: fp64 [N][HRV_DIFFAUG_SLOTS] */
+int hrv_diffaug_gsum_f32(const float* g, int32_t g_cstride, int32_t Ca, const float* u, int32_t policy, int32_t N, int32_t H,
+                         int32_t W, double* part, double* sum, hrv_stream_t stream);
+/* d_img fp32 NCHW [N,3,H,W], every element written; gsum fp64 [N] (may be NULL without HRV_DIFFAUG_COLOR) */
+int hrv_diffaug_bwd_f32(const float* g, int32_t g_cstride, int32_t Ca, const float* u, const double* gsum, int32_t policy, int32_t N,
+                        int32_t H, int32_t W, float* d_img, hrv_stream_t stream);
+
 /* fp32 NCHW (module boundary) <-> bf16 NHWC (inside the bf16 generator path) */
 int hrv_nchw_f32_to_nhwc_bf16(const float* in, int32_t N, int32_t C, int32_t H, int32_t W, uint16_t* out,
                               int32_t out_cstride, int32_t out_coff, int32_t zero_tail, hrv_stream_t stream);

@@ -24,6 +24,9 @@ on the MI355X-native hot path.
     pipeline + generator in eval mode on test items) as PNGs under ``<tensorboard_dir>/<name>/images/``, composed and quantised in one
     HIP launch (hr_viton_amd.viz, which states the deviations).  Without ``--board`` nothing of this is computed or written and
     ``--tensorboard_count`` is ignored.
+  * ``--diffaug color,translation,cutout`` (any subset; default off): DiffAugment of both discriminator calls of an iteration, applied
+    inside the kernels that assemble the PatchGAN input (hr_viton_amd.diffaug).  The VGG term, ``test/LPIPS`` and the grids see the
+    un-augmented output.
 Bug-fixes of the reference call sites: tocg(input1, input2) arity, load_checkpoint arity,
 Adam betas as floats.
 """
@@ -44,6 +47,7 @@ import hr_viton_amd  # noqa: E402,F401
 from hr_viton_amd import dist as hdist  # noqa: E402
 from hr_viton_amd import viz  # noqa: E402
 from hr_viton_amd.checkpoint import load_checkpoint, save_checkpoint  # noqa: E402
+from hr_viton_amd.diffaug import add_diffaug_args, diffaug_from_opt  # noqa: E402
 from hr_viton_amd.gen_train import attach_grad_sync  # noqa: E402
 from hr_viton_amd.losses import GANLoss, L1Loss  # noqa: E402
 from hr_viton_amd.network_generator import MultiscaleDiscriminator, SPADEGenerator  # noqa: E402
@@ -132,6 +136,7 @@ def get_opt(argv=None):
                    help="every --tensorboard_count steps record the loss scalars and the image grids (train_generator.py:364-478)")
     add_guard_args(p)
     add_ema_args(p)
+    add_diffaug_args(p)
     opt = p.parse_args(argv)
     opt.gpu_ids = [int(s) for s in str(opt.gpu_ids).split(",") if s.strip() and int(s) >= 0]
     return opt
@@ -301,6 +306,7 @@ def main(argv=None):
     for s in (sync_g, sync_d):
         if s is not None:
             attach_grad_sync(s)
+    aug = diffaug_from_opt(opt)      # (None without --diffaug: the plain iteration, no new launch)
     lam = lambda step: 1.0 - max(0, step * 1000 + opt.load_step - opt.keep_step) / float(opt.decay_step + 1)  # noqa: E731
     sched_g = torch.optim.lr_scheduler.LambdaLR(opt_g, lr_lambda=lam)
     sched_d = torch.optim.lr_scheduler.LambdaLR(opt_d, lr_lambda=lam)
@@ -330,7 +336,7 @@ def main(argv=None):
         aux = {} if record else None
         x, parse7 = make_generator_inputs(opt, tocg, batch, aux=aux)
         losses, _ = generator_train_step(opt, generator, discriminator, crit_gan, crit_feat, crit_vgg, opt_g, opt_d, x,
-                                         parse7, batch["image"], sync_g, sync_d, aux=aux)
+                                         parse7, batch["image"], sync_g, sync_d, aux=aux, aug=aug)
         if record:
             validation.record(tocg, generator, step, losses, batch, aux, aux["output"])
         if validation_due(step, opt.lpips_count) and validation is not None:        # :480-584
