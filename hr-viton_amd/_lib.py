@@ -179,6 +179,14 @@ HRV_VIZ_MAX_PANELS, HRV_VIZ_MAX_CLASSES = 16, 20
 VIZ_SIGNED, VIZ_UNIT, VIZ_SEGMAP = 0, 1, 2      # hrv_viz_panel_t.kind
 VIZ_ROUND, VIZ_TRUNC = 0, 1                     # hrv_viz_grid_u8's quant
 DIFFAUG_COLOR, DIFFAUG_TRANSLATION, DIFFAUG_CUTOUT = 1, 2, 4      # the policy bits of hrv_diffaug_*
+# hrv_dhead_*: the record of include/hrviton_hip.h (fp64 words)
+DHEAD_MAX_SCALES, DHEAD_SLOTS, DHEAD_WORDS, DHEAD_SCALE_WORDS = 4, 64, 72, 8
+DHEAD_PART_WORDS = 2 * DHEAD_MAX_SCALES * DHEAD_SLOTS * 5
+DHEAD_FORM_PAPER, DHEAD_FORM_RELU = 0, 1
+DHEAD_COUNT, DHEAD_NONFINITE, DHEAD_LAMBDA, DHEAD_REG, DHEAD_STEPS, DHEAD_STATE, DHEAD_SUMS = 0, 1, 2, 3, 4, 8, 40
+DHEAD_ANCHOR_REAL, DHEAD_ANCHOR_FAKE, DHEAD_RT_AVG, DHEAD_RT, DHEAD_MEAN_REAL, DHEAD_MEAN_FAKE, DHEAD_REG_K = range(7)
+(DHEAD_SUM_REAL, DHEAD_SUM_FAKE, DHEAD_SIGN_REAL, DHEAD_HINGE_REAL, DHEAD_HINGE_FAKE, DHEAD_SUMSQ_REAL, DHEAD_SUMSQ_FAKE,
+ DHEAD_NONFINITE_K) = range(8)
 DIFFAUG_SLOTS = 128                             # HRV_DIFFAUG_SLOTS: fp64 partials per sample of hrv_diffaug_mean_f32 / _gsum_f32
 
 
@@ -189,6 +197,7 @@ class hrv_viz_panel_t(C.Structure):
 
 # every symbol include/hrviton_hip.h declares: (restype, argtypes)
 _i32, _i64, _f, _vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
+_d = C.c_double
 _ip = C.POINTER(C.c_int32)
 SYMBOLS = {
     "hrv_version": (C.c_char_p, []),
@@ -301,6 +310,8 @@ SYMBOLS = {
     "hrv_diffaug_concat_f32": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
     "hrv_diffaug_gsum_f32": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "hrv_diffaug_bwd_f32": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "hrv_dhead_forward_f32": (C.c_int, [_i32, _vp, _vp, _vp, _i32, _d, _d, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "hrv_dhead_backward_f32": (C.c_int, [_i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "hrv_resize_bilinear_nhwc_f32": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f, _f,
                                                _vp, _i32, _i32, _vp, _i32, _i32, _vp]),
     "hrv_flow_warp_nhwc_f32": (C.c_int, [C.POINTER(hrv_flow_warp_t), _vp]),

@@ -222,16 +222,21 @@ class GraphedTrainStep:
     label-map activation tensor [N,H,W,8], 'im': [N,3,H,W]} -- static buffers refreshed by ``__call__``.  SPADE noise is
     drawn inside the captured region (torch's graph-safe Philox) unless ``noise`` / ``noise_d`` plane dicts are given
     (then they are static inputs too).  ``aug``: a diffaug.DiffAugment; its uniforms are drawn inside the captured region the
-    same way, so every replay augments anew.  Losses come back as the static tensors of the capture."""
+    same way, so every replay augments anew.  ``lecam``: a lecam.LeCam -- its record is device state the replays advance (count,
+    anchors, the crossing of ``start``); one GPU only: the all-reduce of its sums between graph segments is not built.  Losses come
+    back as the static tensors of the capture."""
 
     def __init__(self, opt, generator, discriminator, crit_gan, crit_feat, crit_vgg, opt_g, opt_d, inputs: Dict[str, torch.Tensor],
-                 noise=None, noise_d=None, warmup: int = 3, aug=None):
+                 noise=None, noise_d=None, warmup: int = 3, aug=None, lecam=None):
         from .ops import Act
         from .pipeline import generator_train_step
         _lib.load()
         for o in (opt_g, opt_d):
             if not getattr(o, "device_step", False):
                 raise HrvError("GraphedTrainStep: build the optimizers with hr_viton_amd.optim.Adam(..., device_step=True)")
+        if lecam is not None and lecam._world() > 1:
+            raise HrvError("GraphedTrainStep: the LeCam loss head all-reduces its logit sums between its two stages, which is not "
+                           "cut into graph segments; under data-parallel training run the iteration eagerly")
         self.opt_g, self.opt_d = opt_g, opt_d
         self.static_in = {k: v.clone() for k, v in inputs.items()}
         self.noise = None if noise is None else {k: [z.clone() for z in v] for k, v in noise.items()}
@@ -241,7 +246,8 @@ class GraphedTrainStep:
             b = self.static_in
             return generator_train_step(opt, generator, discriminator, crit_gan, crit_feat, crit_vgg, opt_g, opt_d, b["x"],
                                         Act(b["parse7"], 7), b["im"], getattr(opt_g, "grad_sync", None),
-                                        getattr(opt_d, "grad_sync", None), noise=self.noise, noise_d=self.noise_d, aug=aug)
+                                        getattr(opt_d, "grad_sync", None), noise=self.noise, noise_d=self.noise_d, aug=aug,
+                                        lecam=lecam)
         self._it = GraphedIteration(body, (opt_g, opt_d), warmup)
         self.graph, self.static_out = self._it.graph, self._it.static_out
         self.replays = 0

@@ -72,13 +72,19 @@ def make_generator_inputs(opt, tocg, inputs: Dict[str, torch.Tensor], aux: Optio
 
 
 def generator_train_step(opt, generator, discriminator, crit_gan, crit_feat, crit_vgg, opt_g, opt_d, x, parse7, im,
-                         sync_g=None, sync_d=None, noise=None, noise_d=None, aux: Optional[dict] = None, aug=None, aug_u=None):
+                         sync_g=None, sync_d=None, noise=None, noise_d=None, aux: Optional[dict] = None, aug=None, aug_u=None,
+                         lecam=None):
     """One G step + one D step of train_generator.py:279-360.  ``parse7``: Act [N,H,W,8] (7 real).  ``aux``: a dictionary that
     receives 'output', the D step's generator output, which is what the reference's recording block shows (:368).
     ``noise`` / ``noise_d``: the SPADE noise draws of the two generator forwards (default: drawn like the reference,
     network_generator.py:104-107); the data-parallel equivalence test injects them.  ``aug``: a diffaug.DiffAugment -- both
     discriminator calls see their [fake ; real] input augmented (what the VGG term and the caller see is not); ``aug_u`` = (u_G, u_D)
-    injects the uniforms of the generator step's and the discriminator step's call (default: two independent draws on the device)."""
+    injects the uniforms of the generator step's and the discriminator step's call (default: two independent draws on the device).
+    ``lecam``: a lecam.LeCam -- the D step's two ``crit_gan`` calls become its fused loss head (hinge terms, logit statistics, anchors
+    and the regulariser in three launches); ``losses`` gains 'D_LeCam'.  The G step is untouched."""
+    if lecam is not None and getattr(crit_gan, "gan_mode", None) != "hinge":
+        raise ops.HrvError("generator_train_step: the LeCam loss head computes the hinge terms of GANLoss('hinge'); this crit_gan is "
+                           "%r" % (getattr(crit_gan, "gan_mode", type(crit_gan).__name__),))
     pair = hasattr(discriminator, "forward_pair") and not getattr(opt, "_hrv_no_pair", False)
     if aug is None and aug_u is not None:
         raise ops.HrvError("generator_train_step: aug_u without aug")
@@ -134,8 +140,11 @@ def generator_train_step(opt, generator, discriminator, crit_gan, crit_feat, cri
     else:
         fake_concat = torch.cat((parse_nchw, output), dim=1)
         pred_fake, pred_real = discriminator(torch.cat((fake_concat, real_concat), dim=0), split=True)
-    d_losses = {"D_Fake": crit_gan(pred_fake, False, for_discriminator=True),
-                "D_Real": crit_gan(pred_real, True, for_discriminator=True)}
+    if lecam is not None:
+        d_losses = lecam.d_losses(pred_fake, pred_real)
+    else:
+        d_losses = {"D_Fake": crit_gan(pred_fake, False, for_discriminator=True),
+                    "D_Real": crit_gan(pred_real, True, for_discriminator=True)}
     loss_dis = sum(d_losses.values()).mean()
     opt_d.zero_grad()
     loss_dis.backward()

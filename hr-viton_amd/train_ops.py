@@ -1226,6 +1226,71 @@ def diffaug_bwd(g: Act, Ca: int, u: torch.Tensor, gsum: Optional[torch.Tensor], 
     return out
 
 
+# ---- fused loss head of the PatchGAN's discriminator step (csrc/dhead.hip; record layout: include/hrviton_hip.h) ----
+def _dhead_desc(x_fake: Sequence[torch.Tensor], x_real: Sequence[torch.Tensor], what: str):
+    k = len(x_fake)
+    if not 1 <= k <= _lib.DHEAD_MAX_SCALES or len(x_real) != k:
+        raise ops.HrvError(f"{what}: 1..{_lib.DHEAD_MAX_SCALES} scales with a fake and a real half each, got {k} / {len(x_real)}")
+    for f, r in zip(x_fake, x_real):
+        for t in (f, r):
+            ops.require_cuda(t, what)
+            if t.dtype != torch.float32 or t.numel() < 1:
+                raise ops.HrvError(f"{what}: the logits are non-empty fp32 tensors, got {t.dtype} {tuple(t.shape)}")
+        if f.numel() != r.numel():
+            raise ops.HrvError(f"{what}: the halves of a scale have {f.numel()} and {r.numel()} elements")
+    ptrs = C.c_void_p * k
+    return (k, ptrs(*[t.data_ptr() for t in x_fake]), ptrs(*[t.data_ptr() for t in x_real]),
+            (C.c_int64 * k)(*[t.numel() for t in x_fake]))
+
+
+def dhead_forward(x_fake, x_real, form: int, weight: float, decay: float, start: int, part: torch.Tensor, record: torch.Tensor,
+                  losses: torch.Tensor, world: int = 1, reduce_sums=None):
+    """Logits -> record and ``losses`` [3] (D_Fake, D_Real, D_LeCam): dhead_reduce + dhead_finalize.  ``x_fake`` / ``x_real``: per
+    scale a DENSE fp32 tensor (the caller saw to that).  ``reduce_sums`` (data parallel, with ``world``): called with the view of the
+    record's sums between the two finalize stages."""
+    lib = _lib.load()
+    k, pf, pr, n = _dhead_desc(x_fake, x_real, "dhead_forward")
+    if part.dtype != torch.float64 or part.numel() < _lib.DHEAD_PART_WORDS or record.dtype != torch.float64 or \
+            record.numel() != _lib.DHEAD_WORDS or losses.dtype != torch.float32 or losses.numel() != 3:
+        raise ops.HrvError(f"dhead_forward: the workspace is {_lib.DHEAD_PART_WORDS} float64 partials, the record {_lib.DHEAD_WORDS} "
+                           "float64 words, the losses 3 floats")
+    total = 8.0 * sum(t.numel() for t in x_fake)
+
+    def call(stage):
+        _lib.check(lib.hrv_dhead_forward_f32(k, pf, pr, n, form, float(weight), float(decay), int(start), int(world), stage,
+                                             part.data_ptr(), record.data_ptr(), losses.data_ptr(), _stream()), "hrv_dhead_forward_f32")
+    with _Timed("dhead", "dhead_reduce", 0.0, total, "dhead_reduce_kernel"):
+        call(1)
+    if reduce_sums is None:
+        with _Timed("dhead", "dhead_finalize", 0.0, 8.0 * _lib.DHEAD_PART_WORDS, "dhead_finalize_kernel"):
+            call(6)
+    else:
+        with _Timed("dhead", "dhead_finalize", 0.0, 8.0 * _lib.DHEAD_PART_WORDS, "dhead_finalize_kernel"):
+            call(2)
+        reduce_sums(record[_lib.DHEAD_SUMS:_lib.DHEAD_SUMS + _lib.DHEAD_SCALE_WORDS * k])
+        with _Timed("dhead", "dhead_finalize", 0.0, 8.0 * _lib.DHEAD_WORDS, "dhead_finalize_kernel"):
+            call(4)
+
+
+def dhead_backward(x_fake, x_real, form: int, record: torch.Tensor, g_fake: torch.Tensor, g_real: torch.Tensor,
+                   g_lecam: torch.Tensor, d_fake, d_real):
+    """The gradients of all logits in one launch (dhead_grad); ``d_fake`` / ``d_real``: per scale an fp32 tensor with the memory
+    layout of its logits, every element written."""
+    lib = _lib.load()
+    k, pf, pr, n = _dhead_desc(x_fake, x_real, "dhead_backward")
+    for g in (g_fake, g_real, g_lecam):
+        if g.dtype != torch.float32 or g.numel() != 1 or not g.is_cuda:
+            raise ops.HrvError("dhead_backward: the three upstream gradients are fp32 device scalars")
+    for xs, ds in ((x_fake, d_fake), (x_real, d_real)):
+        if len(ds) != k or any(d.dtype != torch.float32 or d.numel() != x.numel() or d.stride() != x.stride() for x, d in zip(xs, ds)):
+            raise ops.HrvError("dhead_backward: one fp32 gradient tensor per half, laid out like its logits")
+    ptrs = C.c_void_p * k
+    with _Timed("dhead", "dhead_grad", 0.0, 16.0 * sum(t.numel() for t in x_fake), "dhead_grad_kernel"):
+        _lib.check(lib.hrv_dhead_backward_f32(k, pf, pr, n, form, record.data_ptr(), g_fake.data_ptr(), g_real.data_ptr(),
+                                              g_lecam.data_ptr(), ptrs(*[t.data_ptr() for t in d_fake]),
+                                              ptrs(*[t.data_ptr() for t in d_real]), _stream()), "hrv_dhead_backward_f32")
+
+
 def space_to_depth2(a: Act) -> Act:
     """[N,H,W,C] fp32 -> dense [N,H/2,W/2,4*Cp], channel ((y&1)*2 + (x&1))*Cp + c (hrv_space_to_depth2_nhwc_f32)."""
     lib = _lib.load()

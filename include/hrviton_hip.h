@@ -681,6 +681,76 @@ int hrv_diffaug_gsum_f32(const float* g, int32_t g_cstride, int32_t Ca, const fl
 int hrv_diffaug_bwd_f32(const float* g, int32_t g_cstride, int32_t Ca, const float* u, const double* gsum, int32_t policy, int32_t N,
                         int32_t H, int32_t W, float* d_img, hrv_stream_t stream);
 
+/* Fused loss head of the PatchGAN's discriminator step: hinge terms, logit statistics, LeCam anchors and regulariser (Tseng et al.,
+ * CVPR 2021) and the gradients of all logits, decided ON THE DEVICE (no host read, capturable).  Per scale k < num_d (at most
+ * HRV_DHEAD_MAX_SCALES): x_fake[k] / x_real[k] point at n[k] dense fp32 logits each (any 4-byte-aligned pointer, any n >= 1; nothing
+ * outside is read).  The three pointer / count arrays are HOST arrays, read during the call.
+ *
+ * hrv_dhead_forward_f32.  stage: bit 0 launches the reduce pass (logits -> part), bit 1 a finalize block that turns part into the sums
+ * of the record, bit 2 a finalize block that turns the sums into everything else (bits 1 and 2 together: one launch); 7 = the whole
+ * forward in two launches.  part: HRV_DHEAD_PART_WORDS doubles of scratch.  record:
+ * HRV_DHEAD_WORDS doubles, zeroed once before the first step, every word fp64:
+ *   [HRV_DHEAD_COUNT]      applied anchor updates so far (a poisoned step is not applied)
+ *   [HRV_DHEAD_NONFINITE]  this step's count of non-finite logits, all scales
+ *   [HRV_DHEAD_LAMBDA]     this step's lambda_eff: weight when COUNT, as it stood BEFORE this step, is >= start, else 0
+ *   [HRV_DHEAD_REG]        this step's R, averaged over the scales, before the weight (form relu with lambda_eff == 0: not computed, 0)
+ *   [HRV_DHEAD_STEPS]      steps seen, poisoned ones included
+ *   [HRV_DHEAD_STATE + HRV_DHEAD_SCALE_WORDS * k + ...]   per scale:
+ *     ANCHOR_REAL, ANCHOR_FAKE   a <- d * a + (1 - d) * mean, d = decay, or 0 while COUNT == 0; updated BEFORE they are used
+ *     RT_AVG                     the same average of RT
+ *     RT, MEAN_REAL, MEAN_FAKE   this step's sum sign(x_real) / n (sign(0) = 0), sum x_real / n, sum x_fake / n
+ *     REG_K                      this step's R of the scale
+ *   [HRV_DHEAD_SUMS + HRV_DHEAD_SCALE_WORDS * k + ...]    per scale, this step's raw sums in a fixed order:
+ *     SUM_REAL, SUM_FAKE, SIGN_REAL, HINGE_REAL (sum max(1 - x_r, 0)), HINGE_FAKE (sum max(1 + x_f, 0)), SUMSQ_REAL, SUMSQ_FAKE,
+ *     NONFINITE_K
+ * R = mean((x_r - a_F)^2) + mean((x_f - a_R)^2) (HRV_DHEAD_FORM_PAPER) or mean(relu(x_r - a_F)^2) + mean(relu(a_R - x_f)^2)
+ * (HRV_DHEAD_FORM_RELU, the published code).  losses[0..2] = D_Fake, D_Real (hinge means averaged over the scales) and
+ * D_LeCam = lambda_eff * R, each the fp64 value rounded once.  A poisoned step (NONFINITE != 0) leaves the anchors, RT_AVG and COUNT
+ * alone, reports the hinge means as the sums give them and D_LeCam = NaN.
+ * n_mult multiplies every n in the means: a data-parallel caller all-reduces record[HRV_DHEAD_SUMS ...] between a stage-2 and a
+ * stage-4 call with n_mult = world.  (The relu form's second pass is over the
+ * caller's own logits.)  The slot count, the element -> slot rule and every summation order are fixed and no atomics are used: the
+ * same logits give the same bits in every run and on every card.
+ *
+ * hrv_dhead_backward_f32: one launch.  d_fake[k][i] / d_real[k][i] = (+-1 or 0) * (float)(1 / n) * (g / num_d), g = g_fake[0] /
+ * g_real[0], in fp32 and in that order, plus -- when lambda_eff != 0 -- (g_lecam[0] / num_d) * lambda_eff * dR/dx in fp64, the sum
+ * rounded once.  record is what the forward call of the same step left; the anchors are constants of the gradient. */
+#define HRV_DHEAD_MAX_SCALES 4
+#define HRV_DHEAD_SLOTS 64
+#define HRV_DHEAD_PART_WORDS (2 * HRV_DHEAD_MAX_SCALES * HRV_DHEAD_SLOTS * 5)
+#define HRV_DHEAD_FORM_PAPER 0
+#define HRV_DHEAD_FORM_RELU 1
+#define HRV_DHEAD_COUNT 0
+#define HRV_DHEAD_NONFINITE 1
+#define HRV_DHEAD_LAMBDA 2
+#define HRV_DHEAD_REG 3
+#define HRV_DHEAD_STEPS 4
+#define HRV_DHEAD_STATE 8
+#define HRV_DHEAD_SUMS 40
+#define HRV_DHEAD_SCALE_WORDS 8
+#define HRV_DHEAD_WORDS 72
+#define HRV_DHEAD_ANCHOR_REAL 0
+#define HRV_DHEAD_ANCHOR_FAKE 1
+#define HRV_DHEAD_RT_AVG 2
+#define HRV_DHEAD_RT 3
+#define HRV_DHEAD_MEAN_REAL 4
+#define HRV_DHEAD_MEAN_FAKE 5
+#define HRV_DHEAD_REG_K 6
+#define HRV_DHEAD_SUM_REAL 0
+#define HRV_DHEAD_SUM_FAKE 1
+#define HRV_DHEAD_SIGN_REAL 2
+#define HRV_DHEAD_HINGE_REAL 3
+#define HRV_DHEAD_HINGE_FAKE 4
+#define HRV_DHEAD_SUMSQ_REAL 5
+#define HRV_DHEAD_SUMSQ_FAKE 6
+#define HRV_DHEAD_NONFINITE_K 7
+int hrv_dhead_forward_f32(int32_t num_d, const float* const* x_fake, const float* const* x_real, const int64_t* n, int32_t form,
+                          double weight, double decay, int32_t start, int32_t n_mult, int32_t stage, double* part, double* record,
+                          float* losses, hrv_stream_t stream);
+int hrv_dhead_backward_f32(int32_t num_d, const float* const* x_fake, const float* const* x_real, const int64_t* n, int32_t form,
+                           const double* record, const float* g_fake, const float* g_real, const float* g_lecam,
+                           float* const* d_fake, float* const* d_real, hrv_stream_t stream);
+
 /* fp32 NCHW (module boundary) <-> bf16 NHWC (inside the bf16 generator path) */
 int hrv_nchw_f32_to_nhwc_bf16(const float* in, int32_t N, int32_t C, int32_t H, int32_t W, uint16_t* out,
                               int32_t out_cstride, int32_t out_coff, int32_t zero_tail, hrv_stream_t stream);

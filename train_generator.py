@@ -27,6 +27,11 @@ on the MI355X-native hot path.
   * ``--diffaug color,translation,cutout`` (any subset; default off): DiffAugment of both discriminator calls of an iteration, applied
     inside the kernels that assemble the PatchGAN input (hr_viton_amd.diffaug).  The VGG term, ``test/LPIPS`` and the grids see the
     un-augmented output.
+  * ``--lecam W`` (default 0 = off; ``--lecam_decay 0.99 --lecam_start 0 --lecam_form paper|relu``): the LeCam regulariser of the
+    discriminator step, and ``--d_stats``: the same loss head with weight 0 (mean logits and r_t = E[sign D(real)] only, hinge
+    gradients unchanged) -- hr_viton_amd.lecam.  Anchors, r_t and the count stay on the device; the printed line gains ``D_lecam`` and
+    ``r_t``, ``--board`` records ``Loss/dis/lecam`` and ``Reg/*`` per scale, and ``lecam_step_*.pth`` / ``lecam_final.pth`` are
+    written beside the discriminator's files (``--lecam_checkpoint FILE`` resumes from one).
 Bug-fixes of the reference call sites: tocg(input1, input2) arity, load_checkpoint arity,
 Adam betas as floats.
 """
@@ -49,6 +54,7 @@ from hr_viton_amd import viz  # noqa: E402
 from hr_viton_amd.checkpoint import load_checkpoint, save_checkpoint  # noqa: E402
 from hr_viton_amd.diffaug import add_diffaug_args, diffaug_from_opt  # noqa: E402
 from hr_viton_amd.gen_train import attach_grad_sync  # noqa: E402
+from hr_viton_amd.lecam import add_lecam_args, lecam_from_opt, lecam_line, lecam_scalars  # noqa: E402
 from hr_viton_amd.losses import GANLoss, L1Loss  # noqa: E402
 from hr_viton_amd.network_generator import MultiscaleDiscriminator, SPADEGenerator  # noqa: E402
 from hr_viton_amd.networks import ConditionGenerator  # noqa: E402
@@ -137,6 +143,7 @@ def get_opt(argv=None):
     add_guard_args(p)
     add_ema_args(p)
     add_diffaug_args(p)
+    add_lecam_args(p)
     opt = p.parse_args(argv)
     opt.gpu_ids = [int(s) for s in str(opt.gpu_ids).split(",") if s.strip() and int(s) >= 0]
     return opt
@@ -175,6 +182,7 @@ class _Validation(object):
         self.vis = None
         self.opt_g = self.opt_d = None      # the optimizers whose guard records ride along with the loss scalars (main sets them)
         self.ema_eval = False               # --ema_eval: the test passes run on opt_g's averaged weights (main sets it)
+        self.lecam = None                   # --lecam / --d_stats: the D step's loss head (main sets it)
 
     def weights(self):
         """The context the test passes run in: the generator's averaged weights with --ema_eval, the raw ones otherwise."""
@@ -207,6 +215,10 @@ class _Validation(object):
         self.board.add_scalar("Loss/dis/adv_real", float(losses["D_Real"].mean()), s)
         for tag, val in guard_scalars(self.opt_g, self.opt_d):      # (nothing without --max_grad_norm_* / --skip_nonfinite)
             self.board.add_scalar(tag, val, s)
+        if "D_LeCam" in losses:                                     # (nothing without --lecam / --d_stats)
+            self.board.add_scalar("Loss/dis/lecam", float(losses["D_LeCam"].mean()), s)
+            for tag, val in lecam_scalars(self.lecam):
+                self.board.add_scalar(tag, val, s)
         if opt.num_test_visualize > 0:
             vb = self.vis_batch()
             with self.weights():
@@ -307,6 +319,7 @@ def main(argv=None):
         if s is not None:
             attach_grad_sync(s)
     aug = diffaug_from_opt(opt)      # (None without --diffaug: the plain iteration, no new launch)
+    lecam = lecam_from_opt(opt)      # (None without --lecam / --d_stats: the four GANLoss calls, nothing allocated)
     lam = lambda step: 1.0 - max(0, step * 1000 + opt.load_step - opt.keep_step) / float(opt.decay_step + 1)  # noqa: E731
     sched_g = torch.optim.lr_scheduler.LambdaLR(opt_g, lr_lambda=lam)
     sched_d = torch.optim.lr_scheduler.LambdaLR(opt_d, lr_lambda=lam)
@@ -326,6 +339,7 @@ def main(argv=None):
     if validation is not None:
         validation.opt_g, validation.opt_d = opt_g, opt_d
         validation.ema_eval = bool(ema) and bool(getattr(opt, "ema_eval", False))
+        validation.lecam = lecam
     for step in range(opt.load_step, last):
         t0 = time.time()
         if loader is None:
@@ -336,7 +350,8 @@ def main(argv=None):
         aux = {} if record else None
         x, parse7 = make_generator_inputs(opt, tocg, batch, aux=aux)
         losses, _ = generator_train_step(opt, generator, discriminator, crit_gan, crit_feat, crit_vgg, opt_g, opt_d, x,
-                                         parse7, batch["image"], sync_g, sync_d, aux=aux, aug=aug)
+                                         parse7, batch["image"], sync_g, sync_d, aux=aux, aug=aug,
+                                         **({} if lecam is None else {"lecam": lecam}))
         if record:
             validation.record(tocg, generator, step, losses, batch, aux, aux["output"])
         if validation_due(step, opt.lpips_count) and validation is not None:        # :480-584
@@ -348,13 +363,15 @@ def main(argv=None):
             lg = sum(v.item() for k, v in losses.items() if not k.startswith("D_"))
             print("step: %8d, time: %.3f, G_loss: %.4f, G_adv_loss: %.4f, D_loss: %.4f, D_fake_loss: %.4f, D_real_loss: %.4f"
                   % (step + 1, t, lg, losses["GAN"].item(), ld, losses["D_Fake"].item(), losses["D_Real"].item())
-                  + guard_line(opt_g, opt_d), flush=True)
+                  + guard_line(opt_g, opt_d) + lecam_line(lecam, losses), flush=True)
         if (step + 1) % opt.save_count == 0 and rank == 0:
             save_checkpoint(generator, os.path.join(opt.checkpoint_dir, opt.name, "gen_step_%06d.pth" % (step + 1)), opt)
             save_checkpoint(discriminator, os.path.join(opt.checkpoint_dir, opt.name, "dis_step_%06d.pth" % (step + 1)), opt)
             if ema:
                 save_checkpoint(generator, os.path.join(opt.checkpoint_dir, opt.name, "gen_ema_step_%06d.pth" % (step + 1)), opt,
                                 state_dict=opt_g.ema_state_dict(generator))
+            if lecam is not None:
+                torch.save(lecam.state_dict(), os.path.join(opt.checkpoint_dir, opt.name, "lecam_step_%06d.pth" % (step + 1)))
         if (step + 1) % 1000 == 0:
             sched_g.step()
             sched_d.step()
@@ -364,6 +381,8 @@ def main(argv=None):
         if ema:
             save_checkpoint(generator, os.path.join(opt.checkpoint_dir, opt.name, "gen_ema_model_final.pth"), opt,
                             state_dict=opt_g.ema_state_dict(generator))
+        if lecam is not None:
+            torch.save(lecam.state_dict(), os.path.join(opt.checkpoint_dir, opt.name, "lecam_final.pth"))
         validation.board.close()
         print("Finished training %s!" % opt.name)
 
