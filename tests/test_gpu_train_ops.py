@@ -76,6 +76,25 @@ def test_pack_dev_equals_host_pack():
         assert torch.equal(dev, host)
 
 
+def test_pack_dev_bf16_equals_host_pack():
+    """the same comparison for the bf16 form: 32 k-values per row (cfg 1) and 64 (cfg 9), on the raw bf16 bits"""
+    import ctypes as C
+    ops, T = _mods()
+    from hr_viton_amd import _lib
+    lib = _lib.load()
+    g = torch.Generator().manual_seed(0)
+    w = torch.randn(40, 96 + 16 + 4, 3, 3, generator=g)
+    srcC = (C.c_int32 * 3)(96, 16, 4)
+    for cfg in (1, 9):
+        elems = lib.hrv_conv2d_packed_elems_bf16(40, 3, 3, 3, srcC, cfg)
+        host = torch.full((elems,), 0x7FC1, dtype=torch.int16)
+        assert lib.hrv_conv2d_pack_weight_bf16(w.data_ptr(), 40, 3, 3, 3, srcC, srcC, cfg, host.data_ptr()) == 0
+        dev, geom = T.pack_weight_dev(w.cuda(), [96, 16, 4], [96, 16, 4], cfg, 0, 1, 1, bf16=True)
+        assert dev.dtype == torch.bfloat16 and dev.numel() == elems == geom[7]
+        assert geom[6] == (3 + 1 + 1 if cfg == 1 else 2 + 1 + 1)
+        assert torch.equal(dev.view(torch.int16).cpu(), host)
+
+
 def test_dgrad_fused_activation_derivative_and_accumulate():
     ops, T = _mods()
     g = torch.Generator().manual_seed(5)
