@@ -187,6 +187,8 @@ DHEAD_COUNT, DHEAD_NONFINITE, DHEAD_LAMBDA, DHEAD_REG, DHEAD_STEPS, DHEAD_STATE,
 DHEAD_ANCHOR_REAL, DHEAD_ANCHOR_FAKE, DHEAD_RT_AVG, DHEAD_RT, DHEAD_MEAN_REAL, DHEAD_MEAN_FAKE, DHEAD_REG_K = range(7)
 (DHEAD_SUM_REAL, DHEAD_SUM_FAKE, DHEAD_SIGN_REAL, DHEAD_HINGE_REAL, DHEAD_HINGE_FAKE, DHEAD_SUMSQ_REAL, DHEAD_SUMSQ_FAKE,
  DHEAD_NONFINITE_K) = range(8)
+ADA_WORDS = 8                                   # hrv_ada_update_f64: the controller's state (fp64 words)
+ADA_P, ADA_ACC, ADA_SEEN, ADA_UPDATES, ADA_RT_WINDOW, ADA_STEPS, ADA_RT_LAST = range(7)
 DIFFAUG_SLOTS = 128                             # HRV_DIFFAUG_SLOTS: fp64 partials per sample of hrv_diffaug_mean_f32 / _gsum_f32
 
 
@@ -310,6 +312,10 @@ SYMBOLS = {
     "hrv_diffaug_concat_f32": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
     "hrv_diffaug_gsum_f32": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "hrv_diffaug_bwd_f32": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "hrv_diffaug_concat_gated_f32": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "hrv_diffaug_gsum_gated_f32": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "hrv_diffaug_bwd_gated_f32": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "hrv_ada_update_f64": (C.c_int, [_vp, _i32, _d, _d, _i32, _d, _vp, _vp]),
     "hrv_dhead_forward_f32": (C.c_int, [_i32, _vp, _vp, _vp, _i32, _d, _d, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "hrv_dhead_backward_f32": (C.c_int, [_i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "hrv_resize_bilinear_nhwc_f32": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f, _f,

@@ -4,6 +4,10 @@
 //   diffaug_concat_kernel  the augmenting twin of concat_nhwc_nchw_v4_kernel (sample.hip): gather, select, color
 //   diffaug_gsum_kernel    per-sample sum of the selected gradient over the three image channels (color only)
 //   diffaug_bwd_kernel     the augmenting twin of the to_nchw slice that extracts d(fake): the adjoint, every element written
+// The three kernels that read the policy are templates (template <bool GATED, typename... Gate>): the gated instances (ADA, Karras
+// et al. 2020) take two more arguments and narrow the policy per sample from the gate uniforms ug [N][4] and the probability p[0]
+// in the scalar decode at the top; the ungated instances have an empty pack, the parameters and the body they always had.
+//   ada_update_kernel      the controller that moves p from the loss head's r_t (one thread, eight fp64 words of state)
 // Geometry is a pure gather and select: a masked pixel is never loaded and the address of an out-of-range source is never
 // formed, so nothing a masked source (forward) or a masked destination gradient (backward) holds can reach the result.
 // Color is evaluated in fp64 from the fp32 decode and rounded once.  Determinism of the two reductions as in grad_guard.hip:
@@ -50,6 +54,23 @@ __device__ __forceinline__ AugGeom aug_geom(const float* __restrict__ un, int fl
 
 __device__ __forceinline__ bool aug_in_box(const AugGeom& g, int y, int x) { return y >= g.y0 && y < g.y1 && x >= g.x0 && x < g.x1; }
 __device__ __forceinline__ bool aug_inside(int y, int x, int H, int W) { return (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W; }
+
+// The effective policy of sample n.  An ungated instance has no gate arguments (an empty pack: the parameter list it always had)
+// and takes the policy as it is; a gated one gets (ug [N][4], p) and keeps a transform only where (double)ug < p[0], strict, in
+// fp64 -- block-uniform like u's row: scalar loads, a scalar result.
+template <bool GATED>
+__device__ __forceinline__ int aug_flags(int policy, int) {
+  static_assert(!GATED, "a gated instance takes (ug, p)");
+  return policy;
+}
+template <bool GATED>
+__device__ __forceinline__ int aug_flags(int policy, int n, const float* __restrict__ ug, const double* __restrict__ p) {
+  static_assert(GATED, "an ungated instance takes no gate");
+  const float* __restrict__ gn = ug + (size_t)n * 4;
+  const double pv = p[0];
+  return policy & (((double)gn[0] < pv ? HRV_DIFFAUG_COLOR : 0) | ((double)gn[1] < pv ? HRV_DIFFAUG_TRANSLATION : 0) |
+                   ((double)gn[2] < pv ? HRV_DIFFAUG_CUTOUT : 0));
+}
 
 // the 256 partial sums of a block -> thread 0, fixed order: shuffle tree inside each wave, then waves 0..3 in turn
 __device__ __forceinline__ void aug_block_sum(double& s) {
@@ -114,11 +135,13 @@ __device__ __forceinline__ void aug_pick3(const f32x4 r0, const f32x4 r1, const 
 
 // One thread per DESTINATION pixel: the parse row of the source as two 16-byte loads, the three plane reads coalesced across the
 // wave (the source is the destination shifted by whole pixels), three 16-byte stores.  V == 0: twelve zeros, nothing loaded.
+template <bool GATED, typename... Gate>
 __global__ __launch_bounds__(AUG_BLOCK) void diffaug_concat_kernel(const float* __restrict__ a, int Ca, const float* __restrict__ b,
-                                                                   const float* __restrict__ u, const float* __restrict__ M, int flags,
-                                                                   int H, int W, float* __restrict__ out) {
+                                                                   const float* __restrict__ u, const float* __restrict__ M,
+                                                                   int policy, int H, int W, float* __restrict__ out, Gate... gate) {
   const int n = blockIdx.y, HW = H * W;      // (the sample is uniform over the block: its decode lives in scalar registers)
   const float* __restrict__ un = u + (size_t)n * 8;
+  const int flags = aug_flags<GATED>(policy, n, gate...);
   const AugGeom g = aug_geom(un, flags, H, W);
   for (int p = blockIdx.x * AUG_BLOCK + threadIdx.x; p < HW; p += gridDim.x * AUG_BLOCK) {
     const int y = p / W, x = p - y * W;
@@ -155,9 +178,11 @@ __global__ __launch_bounds__(AUG_BLOCK) void diffaug_concat_kernel(const float* 
 }
 
 // G = V ? g : 0 summed over the destination pixels and the three image channels of sample blockIdx.y (slot blockIdx.x)
+template <bool GATED, typename... Gate>
 __global__ __launch_bounds__(AUG_BLOCK) void diffaug_gsum_kernel(const float* __restrict__ gr, int Ca, const float* __restrict__ u,
-                                                                 int flags, int H, int W, double* __restrict__ part) {
+                                                                 int policy, int H, int W, double* __restrict__ part, Gate... gate) {
   const int n = blockIdx.y, HW = H * W;
+  const int flags = aug_flags<GATED>(policy, n, gate...);
   const AugGeom g = aug_geom(u + (size_t)n * 8, flags, H, W);
   double s = 0.0;
   for (int p = blockIdx.x * AUG_BLOCK + threadIdx.x; p < HW; p += AUG_SLOTS * AUG_BLOCK) {
@@ -175,11 +200,13 @@ __global__ __launch_bounds__(AUG_BLOCK) void diffaug_gsum_kernel(const float* __
 
 // One thread per SOURCE pixel (y', x') of d(image): the destination that read it is (y' - ty, x' - tx).  Reads that destination's
 // gradient row (48 contiguous bytes a lane), writes the three planes coalesced.  Every element of d_img is written.
+template <bool GATED, typename... Gate>
 __global__ __launch_bounds__(AUG_BLOCK) void diffaug_bwd_kernel(const float* __restrict__ gr, int Ca, const float* __restrict__ u,
-                                                                const double* __restrict__ gsum, int flags, int H, int W,
-                                                                float* __restrict__ d_img) {
+                                                                const double* __restrict__ gsum, int policy, int H, int W,
+                                                                float* __restrict__ d_img, Gate... gate) {
   const int n = blockIdx.y, HW = H * W;
   const float* __restrict__ un = u + (size_t)n * 8;
+  const int flags = aug_flags<GATED>(policy, n, gate...);
   const AugGeom g = aug_geom(un, flags, H, W);
   for (int p = blockIdx.x * AUG_BLOCK + threadIdx.x; p < HW; p += gridDim.x * AUG_BLOCK) {
     const int y = p / W, x = p - y * W;
@@ -203,6 +230,32 @@ __global__ __launch_bounds__(AUG_BLOCK) void diffaug_bwd_kernel(const float* __r
     dp[(size_t)HW] = v[1];
     dp[2 * (size_t)HW] = v[2];
   }
+}
+
+// The ADA controller (the order of every operation is the header's): one thread, all words fp64.  s * step is exact (s is -1, 0 or
+// 1), so a contraction into a fused multiply-add gives the same bits.
+__global__ void ada_update_kernel(const double* __restrict__ rec, int num_d, double target, double step, int interval, double p_max,
+                                  double* __restrict__ st) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  st[HRV_ADA_STEPS] += 1.0;
+  if (rec[HRV_DHEAD_NONFINITE] != 0.0) return;
+  double sum = 0.0;
+  for (int k = 0; k < num_d; ++k) sum += rec[HRV_DHEAD_STATE + HRV_DHEAD_SCALE_WORDS * k + HRV_DHEAD_RT];
+  const double r = sum / (double)num_d;
+  st[HRV_ADA_RT_LAST] = r;
+  const double acc = st[HRV_ADA_ACC] + r, seen = st[HRV_ADA_SEEN] + 1.0;
+  if (seen != (double)interval) {
+    st[HRV_ADA_ACC] = acc;
+    st[HRV_ADA_SEEN] = seen;
+    return;
+  }
+  const double m = acc / (double)interval;
+  const double s = (double)((m > target) - (m < target));
+  st[HRV_ADA_RT_WINDOW] = m;
+  st[HRV_ADA_P] = fmin(fmax(st[HRV_ADA_P] + s * step, 0.0), p_max);
+  st[HRV_ADA_ACC] = 0.0;
+  st[HRV_ADA_SEEN] = 0.0;
+  st[HRV_ADA_UPDATES] += 1.0;
 }
 
 // blocks over the pixels of ONE sample (the grid's y is the sample): 256 CUs x 16 blocks over the batch, grid-stride the rest
@@ -247,7 +300,7 @@ extern "C" int hrv_diffaug_concat_f32(const float* a, int32_t Ca, int32_t a_cstr
   HRV_REQUIRE((((uintptr_t)a | (uintptr_t)out) & 15) == 0 && (((uintptr_t)b | (uintptr_t)u | (uintptr_t)mean) & 3) == 0,
               "diffaug_concat: misaligned pointer");
   HRV_REQUIRE(mean || !(policy & HRV_DIFFAUG_COLOR), "diffaug_concat: color needs the per-sample means");
-  hipLaunchKernelGGL(diffaug_concat_kernel, aug_grid_for(H * W, N), dim3(AUG_BLOCK), 0, (hipStream_t)stream, a, (int)Ca, b, u, mean, (int)policy,
+  hipLaunchKernelGGL(diffaug_concat_kernel<false>, aug_grid_for(H * W, N), dim3(AUG_BLOCK), 0, (hipStream_t)stream, a, (int)Ca, b, u, mean, (int)policy,
                      (int)H, (int)W, out);
   return check_launch("diffaug_concat_kernel");
 }
@@ -258,7 +311,7 @@ extern "C" int hrv_diffaug_gsum_f32(const float* g, int32_t g_cstride, int32_t C
   HRV_REQUIRE(Ca >= 1 && Ca <= 8 && g_cstride == 12, "diffaug_gsum: serves the PatchGAN shape only (gradient stride 12, C <= 8 + 3)");
   HRV_REQUIRE(((uintptr_t)g & 15) == 0 && ((uintptr_t)u & 3) == 0 && (((uintptr_t)part | (uintptr_t)sum) & 7) == 0,
               "diffaug_gsum: misaligned pointer");
-  hipLaunchKernelGGL(diffaug_gsum_kernel, dim3(AUG_SLOTS, N), dim3(AUG_BLOCK), 0, (hipStream_t)stream, g, (int)Ca, u, (int)policy, (int)H,
+  hipLaunchKernelGGL(diffaug_gsum_kernel<false>, dim3(AUG_SLOTS, N), dim3(AUG_BLOCK), 0, (hipStream_t)stream, g, (int)Ca, u, (int)policy, (int)H,
                      (int)W, part);
   int rc = check_launch("diffaug_gsum_kernel");
   if (rc != HRV_OK) return rc;
@@ -274,7 +327,66 @@ extern "C" int hrv_diffaug_bwd_f32(const float* g, int32_t g_cstride, int32_t Ca
   HRV_REQUIRE(((uintptr_t)g & 15) == 0 && (((uintptr_t)u | (uintptr_t)d_img) & 3) == 0 && ((uintptr_t)gsum & 7) == 0,
               "diffaug_bwd: misaligned pointer");
   HRV_REQUIRE(gsum || !(policy & HRV_DIFFAUG_COLOR), "diffaug_bwd: color needs the per-sample gradient sums");
-  hipLaunchKernelGGL(diffaug_bwd_kernel, aug_grid_for(H * W, N), dim3(AUG_BLOCK), 0, (hipStream_t)stream, g, (int)Ca, u, gsum, (int)policy, (int)H,
+  hipLaunchKernelGGL(diffaug_bwd_kernel<false>, aug_grid_for(H * W, N), dim3(AUG_BLOCK), 0, (hipStream_t)stream, g, (int)Ca, u, gsum, (int)policy, (int)H,
                      (int)W, d_img);
   return check_launch("diffaug_bwd_kernel");
+}
+
+static inline bool aug_gate_ok(const float* ug, const double* p) {
+  return ug && p && ((uintptr_t)ug & 3) == 0 && ((uintptr_t)p & 7) == 0;
+}
+
+extern "C" int hrv_diffaug_concat_gated_f32(const float* a, int32_t Ca, int32_t a_cstride, const float* b, const float* u,
+                                            const float* mean, int32_t policy, int32_t N, int32_t H, int32_t W, float* out,
+                                            int32_t out_cstride, const float* ug, const double* p, hrv_stream_t stream) {
+  HRV_REQUIRE(a && b && u && out && aug_shape_ok(N, H, W) && aug_policy_ok(policy), "diffaug_concat_gated: bad args");
+  HRV_REQUIRE(Ca >= 1 && Ca <= 8 && a_cstride == 8 && out_cstride == 12,
+              "diffaug_concat_gated: serves the PatchGAN shape only (parse stride 8 with C <= 8, 3 image channels, output stride 12)");
+  HRV_REQUIRE((((uintptr_t)a | (uintptr_t)out) & 15) == 0 && (((uintptr_t)b | (uintptr_t)u | (uintptr_t)mean) & 3) == 0 &&
+                  aug_gate_ok(ug, p),
+              "diffaug_concat_gated: misaligned or missing pointer");
+  HRV_REQUIRE(mean || !(policy & HRV_DIFFAUG_COLOR), "diffaug_concat_gated: color needs the per-sample means");
+  hipLaunchKernelGGL((diffaug_concat_kernel<true, const float*, const double*>), aug_grid_for(H * W, N), dim3(AUG_BLOCK), 0, (hipStream_t)stream, a, (int)Ca, b, u, mean,
+                     (int)policy, (int)H, (int)W, out, ug, p);
+  return check_launch("diffaug_concat_kernel<gated>");
+}
+
+extern "C" int hrv_diffaug_gsum_gated_f32(const float* g, int32_t g_cstride, int32_t Ca, const float* u, int32_t policy, int32_t N,
+                                          int32_t H, int32_t W, double* part, double* sum, const float* ug, const double* p,
+                                          hrv_stream_t stream) {
+  HRV_REQUIRE(g && u && part && sum && aug_shape_ok(N, H, W) && aug_policy_ok(policy), "diffaug_gsum_gated: bad args");
+  HRV_REQUIRE(Ca >= 1 && Ca <= 8 && g_cstride == 12, "diffaug_gsum_gated: serves the PatchGAN shape only (gradient stride 12, C <= 8 + 3)");
+  HRV_REQUIRE(((uintptr_t)g & 15) == 0 && ((uintptr_t)u & 3) == 0 && (((uintptr_t)part | (uintptr_t)sum) & 7) == 0 && aug_gate_ok(ug, p),
+              "diffaug_gsum_gated: misaligned or missing pointer");
+  hipLaunchKernelGGL((diffaug_gsum_kernel<true, const float*, const double*>), dim3(AUG_SLOTS, N), dim3(AUG_BLOCK), 0, (hipStream_t)stream, g, (int)Ca, u, (int)policy,
+                     (int)H, (int)W, part, ug, p);
+  int rc = check_launch("diffaug_gsum_kernel<gated>");
+  if (rc != HRV_OK) return rc;
+  hipLaunchKernelGGL(diffaug_finalize_kernel, dim3(N), dim3(AUG_BLOCK), 0, (hipStream_t)stream, (const double*)part, 1.0, (float*)nullptr,
+                     sum);
+  return check_launch("diffaug_finalize_kernel");
+}
+
+extern "C" int hrv_diffaug_bwd_gated_f32(const float* g, int32_t g_cstride, int32_t Ca, const float* u, const double* gsum, int32_t policy,
+                                         int32_t N, int32_t H, int32_t W, float* d_img, const float* ug, const double* p,
+                                         hrv_stream_t stream) {
+  HRV_REQUIRE(g && u && d_img && aug_shape_ok(N, H, W) && aug_policy_ok(policy), "diffaug_bwd_gated: bad args");
+  HRV_REQUIRE(Ca >= 1 && Ca <= 8 && g_cstride == 12, "diffaug_bwd_gated: serves the PatchGAN shape only (gradient stride 12, C <= 8 + 3)");
+  HRV_REQUIRE(((uintptr_t)g & 15) == 0 && (((uintptr_t)u | (uintptr_t)d_img) & 3) == 0 && ((uintptr_t)gsum & 7) == 0 && aug_gate_ok(ug, p),
+              "diffaug_bwd_gated: misaligned or missing pointer");
+  HRV_REQUIRE(gsum || !(policy & HRV_DIFFAUG_COLOR), "diffaug_bwd_gated: color needs the per-sample gradient sums");
+  hipLaunchKernelGGL((diffaug_bwd_kernel<true, const float*, const double*>), aug_grid_for(H * W, N), dim3(AUG_BLOCK), 0, (hipStream_t)stream, g, (int)Ca, u, gsum,
+                     (int)policy, (int)H, (int)W, d_img, ug, p);
+  return check_launch("diffaug_bwd_kernel<gated>");
+}
+
+extern "C" int hrv_ada_update_f64(const double* dhead_record, int32_t num_d, double target, double step, int32_t interval, double p_max,
+                                  double* state, hrv_stream_t stream) {
+  HRV_REQUIRE(dhead_record && state && (((uintptr_t)dhead_record | (uintptr_t)state) & 7) == 0, "ada_update: missing or misaligned pointer");
+  HRV_REQUIRE(num_d >= 1 && num_d <= HRV_DHEAD_MAX_SCALES && interval >= 1, "ada_update: 1..HRV_DHEAD_MAX_SCALES scales, interval >= 1");
+  HRV_REQUIRE(target >= -1.0 && target <= 1.0 && step >= 0.0 && step <= 1.0 && p_max >= 0.0 && p_max <= 1.0,
+              "ada_update: target in [-1, 1], step and p_max in [0, 1]");
+  hipLaunchKernelGGL(ada_update_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, dhead_record, (int)num_d, target, step, (int)interval,
+                     p_max, state);
+  return check_launch("ada_update_kernel");
 }

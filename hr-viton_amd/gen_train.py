@@ -1361,7 +1361,8 @@ class _DiscPairFn(torch.autograd.Function):
 
     ``aug``: None, or (policy bits, u [N,8]) -- DiffAugment (diffaug.py): the two assembly launches and the extraction of d(fake)
     are replaced by their augmenting twins (csrc/diffaug.hip), both halves under the same uniforms; with color, one launch
-    for the image means of both halves in front and one for the gradient sums behind."""
+    for the image means of both halves in front and one for the gradient sums behind.  (policy bits, u, ug [N,4], p) --
+    AdaptiveAugment: the same launches in their gated form, every transform of a sample under its gate ug < p."""
 
     @staticmethod
     def forward(ctx, msd, plan, parse7, fake, real, aug, *params):
@@ -1372,11 +1373,16 @@ class _DiscPairFn(torch.autograd.Function):
         if aug is None:
             T.concat_nhwc_nchw(parse7, fake.detach(), Act(a.t[:N], Ca + Cb))
             T.concat_nhwc_nchw(parse7, real.detach(), Act(a.t[N:], Ca + Cb))
-        else:
+        elif len(aug) == 2:
             flags, u = aug
             mean = T.diffaug_mean(fake.detach(), real.detach()) if flags & _lib.DIFFAUG_COLOR else None
             T.diffaug_concat(parse7, fake.detach(), u, None if mean is None else mean[:N], flags, Act(a.t[:N], Ca + Cb))
             T.diffaug_concat(parse7, real.detach(), u, None if mean is None else mean[N:], flags, Act(a.t[N:], Ca + Cb))
+        else:      # the gated twins: both halves under the same gates too
+            flags, u, ug, p = aug
+            mean = T.diffaug_mean(fake.detach(), real.detach()) if flags & _lib.DIFFAUG_COLOR else None
+            T.diffaug_concat_gated(parse7, fake.detach(), u, None if mean is None else mean[:N], flags, Act(a.t[:N], Ca + Cb), ug, p)
+            T.diffaug_concat_gated(parse7, real.detach(), u, None if mean is None else mean[N:], flags, Act(a.t[N:], Ca + Cb), ug, p)
         ctx.aug = aug
         feats_all, saved = plan.forward(None, power_iteration=True, a=a)
         ctx.plan, ctx.saved, ctx.params, ctx.split = plan, saved, params, True
@@ -1394,26 +1400,32 @@ class _DiscPairFn(torch.autograd.Function):
         d_fake = None
         if d_in is not None and ctx.aug is None:
             d_fake = ops.to_nchw(Act(d_in.t[:N], Ca + Cb), Ca, Cb)      # channels [Ca, Ca+Cb) of the fake half
-        elif d_in is not None:      # the adjoint of the augmented assembly of the fake half
+        elif d_in is not None and len(ctx.aug) == 2:      # the adjoint of the augmented assembly of the fake half
             flags, u = ctx.aug
             g = Act(d_in.t[:N], Ca + Cb)
             d_fake = T.diffaug_bwd(g, Ca, u, T.diffaug_gsum(g, Ca, u, flags) if flags & _lib.DIFFAUG_COLOR else None, flags)
+        elif d_in is not None:      # (the gates read p as it stands now: the controller runs in the D step, whose pass has no d(fake))
+            flags, u, ug, p = ctx.aug
+            g = Act(d_in.t[:N], Ca + Cb)
+            gsum = T.diffaug_gsum_gated(g, Ca, u, flags, ug, p) if flags & _lib.DIFFAUG_COLOR else None
+            d_fake = T.diffaug_bwd_gated(g, Ca, u, gsum, flags, ug, p)
         return (None, None, None, d_fake, None, None) + tuple(grads.get(p) for p in ctx.params)
 
 
 def discriminator_train_forward_pair(msd: nn.Module, parse7: Act, fake: torch.Tensor, real: torch.Tensor, aug=None, aug_u=None):
     """discriminator(cat((cat((parse, fake), 1), cat((parse, real), 1)), 0)) of train_generator.py:283-295, returning
     (pred_fake, pred_real) like ``discriminator_train_forward(..., split=True)`` -- see _DiscPairFn.  ``aug``: a
-    diffaug.DiffAugment (default None: the plain assembly, no other launch); ``aug_u``: its uniforms [N,8] (default: drawn here)."""
+    diffaug.DiffAugment (default None: the plain assembly, no other launch); ``aug_u``: its uniforms [N,8] (default: drawn here);
+    with a diffaug.AdaptiveAugment ``aug_u`` is a (u [N,8], ug [N,4]) pair."""
     ops.require_cuda(fake, "MultiscaleDiscriminator.forward_pair")
     if aug is None and aug_u is not None:
         raise _lib.HrvError("forward_pair: aug_u without aug")
     if aug is not None:
-        from .diffaug import check_u
+        from .diffaug import resolve_aug
         N = fake.shape[0]
         if parse7.cstride != 8 or parse7.coff != 0 or fake.shape[1] != 3:
             raise _lib.HrvError("forward_pair: DiffAugment serves the PatchGAN shape only (parse map with channel stride 8, 3 image channels)")
-        aug = (aug.flags, aug.draw(N, fake.device) if aug_u is None else check_u(aug_u, N, fake.device, "forward_pair"))
+        aug = resolve_aug(aug, aug_u, N, fake.device, "forward_pair")
     plan = getattr(msd, "_train_plan", None)
     if plan is None:
         plan = msd._train_plan = MultiscaleDTrainPlan(msd)

@@ -222,9 +222,10 @@ class GraphedTrainStep:
     label-map activation tensor [N,H,W,8], 'im': [N,3,H,W]} -- static buffers refreshed by ``__call__``.  SPADE noise is
     drawn inside the captured region (torch's graph-safe Philox) unless ``noise`` / ``noise_d`` plane dicts are given
     (then they are static inputs too).  ``aug``: a diffaug.DiffAugment; its uniforms are drawn inside the captured region the
-    same way, so every replay augments anew.  ``lecam``: a lecam.LeCam -- its record is device state the replays advance (count,
-    anchors, the crossing of ``start``); one GPU only: the all-reduce of its sums between graph segments is not built.  Losses come
-    back as the static tensors of the capture."""
+    same way, so every replay augments anew; a diffaug.AdaptiveAugment has its gate draw, its gated launches and (adaptive form,
+    which needs ``lecam``) its controller launch inside the capture too: p is device state the replays advance.  ``lecam``: a
+    lecam.LeCam -- its record is device state the replays advance (count, anchors, the crossing of ``start``); one GPU only: the
+    all-reduce of its sums between graph segments is not built.  Losses come back as the static tensors of the capture."""
 
     def __init__(self, opt, generator, discriminator, crit_gan, crit_feat, crit_vgg, opt_g, opt_d, inputs: Dict[str, torch.Tensor],
                  noise=None, noise_d=None, warmup: int = 3, aug=None, lecam=None):

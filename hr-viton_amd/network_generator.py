@@ -625,7 +625,9 @@ class MultiscaleDiscriminator(BaseNetwork):
         train_generator.py:283-295 -- with the input assembled NHWC by one kernel per half instead of three torch.cat's
         and a layout pass; ``parse7``: the label-map activation (ops.Act), ``fake`` / ``real``: NCHW images.  ``aug``: a
         diffaug.DiffAugment -- parse map, fake and real image of a sample are augmented under ONE row of the uniforms ``aug_u``
-        [N,8] (default: drawn on the device), inside the assembly kernels; d(fake) is the transform's adjoint."""
+        [N,8] (default: drawn on the device), inside the assembly kernels; d(fake) is the transform's adjoint.  A
+        diffaug.AdaptiveAugment runs the same kernels gated: ``aug_u`` is then a (u [N,8], ug [N,4]) pair and sample n keeps a
+        transform only where ug[n] lies below the probability on the device."""
         assert self.training, "forward_pair is the training-step form"
         from .gen_train import discriminator_train_forward_pair
         return discriminator_train_forward_pair(self, parse7, fake.contiguous(), real.contiguous(), aug=aug, aug_u=aug_u)

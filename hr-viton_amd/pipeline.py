@@ -81,13 +81,20 @@ def generator_train_step(opt, generator, discriminator, crit_gan, crit_feat, cri
     discriminator calls see their [fake ; real] input augmented (what the VGG term and the caller see is not); ``aug_u`` = (u_G, u_D)
     injects the uniforms of the generator step's and the discriminator step's call (default: two independent draws on the device).
     ``lecam``: a lecam.LeCam -- the D step's two ``crit_gan`` calls become its fused loss head (hinge terms, logit statistics, anchors
-    and the regulariser in three launches); ``losses`` gains 'D_LeCam'.  The G step is untouched."""
+    and the regulariser in three launches); ``losses`` gains 'D_LeCam'.  The G step is untouched.  With a diffaug.AdaptiveAugment
+    as ``aug`` the assemblies run gated, ``aug_u`` entries are (u, ug) pairs, and -- adaptive form -- one controller launch follows
+    the loss head's forward: the D step of iteration t sets the p both discriminator calls of iteration t + 1 see (it needs
+    ``lecam``; a step the gradient guard skips later is not rolled back in the controller)."""
     if lecam is not None and getattr(crit_gan, "gan_mode", None) != "hinge":
         raise ops.HrvError("generator_train_step: the LeCam loss head computes the hinge terms of GANLoss('hinge'); this crit_gan is "
                            "%r" % (getattr(crit_gan, "gan_mode", type(crit_gan).__name__),))
     pair = hasattr(discriminator, "forward_pair") and not getattr(opt, "_hrv_no_pair", False)
     if aug is None and aug_u is not None:
         raise ops.HrvError("generator_train_step: aug_u without aug")
+    adaptive = getattr(aug, "adaptive", False)
+    if adaptive and lecam is None:
+        raise ops.HrvError("generator_train_step: an adaptive AdaptiveAugment follows the r_t of the loss head; pass lecam= "
+                           "(lecam.LeCam(0.0) keeps the statistics only)")
     if aug is not None and not pair:
         raise ops.HrvError("generator_train_step: DiffAugment lives in the discriminator's pair form (forward_pair); this "
                            "discriminator / opt._hrv_no_pair takes the concatenated-batch form, which is not augmented")
@@ -142,6 +149,8 @@ def generator_train_step(opt, generator, discriminator, crit_gan, crit_feat, cri
         pred_fake, pred_real = discriminator(torch.cat((fake_concat, real_concat), dim=0), split=True)
     if lecam is not None:
         d_losses = lecam.d_losses(pred_fake, pred_real)
+        if adaptive:      # (the head's sums are all-reduced: every rank computes the same r and the same p)
+            aug.update(lecam, im.shape[0] * lecam._world())
     else:
         d_losses = {"D_Fake": crit_gan(pred_fake, False, for_discriminator=True),
                     "D_Real": crit_gan(pred_real, True, for_discriminator=True)}

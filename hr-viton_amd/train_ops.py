@@ -1226,6 +1226,74 @@ def diffaug_bwd(g: Act, Ca: int, u: torch.Tensor, gsum: Optional[torch.Tensor], 
     return out
 
 
+# ---- the gated twins (adaptive discriminator augmentation): sample n keeps a transform only where ug[n, column] < p ----
+def _check_gate(ug: torch.Tensor, p: torch.Tensor, N: int, what: str):
+    if not (isinstance(ug, torch.Tensor) and tuple(ug.shape) == (N, 4) and ug.dtype == torch.float32 and ug.is_contiguous()):
+        raise _lib.HrvError(f"{what}: the gate uniforms are a contiguous fp32 [{N}, 4] tensor")
+    if not (isinstance(p, torch.Tensor) and p.numel() == 1 and p.dtype == torch.float64 and p.device == ug.device):
+        raise _lib.HrvError(f"{what}: p is ONE fp64 word on the device of the uniforms")
+
+
+def diffaug_concat_gated(a: Act, b: torch.Tensor, u: torch.Tensor, mean: Optional[torch.Tensor], policy: int, out: Act,
+                         ug: torch.Tensor, p: torch.Tensor):
+    """``diffaug_concat`` under the per-sample gates ``ug`` [N,4] (color, translation, cutout, spare) and the probability ``p``
+    (one fp64 word on the device, read by the kernel) -- hrv_diffaug_concat_gated_f32."""
+    lib = _lib.load()
+    N, Cb, H, W = b.shape
+    assert (a.N, a.H, a.W) == (N, H, W) == (out.N, out.H, out.W) and not a.bf16 and not out.bf16 and a.coff == 0 and out.coff == 0
+    assert b.is_contiguous() and b.dtype == torch.float32 and out.C == a.C + Cb and out.t.is_contiguous() and a.t.is_contiguous()
+    assert tuple(u.shape) == (N, 8) and u.dtype == torch.float32 and u.is_contiguous()
+    assert mean is None or (mean.numel() == N and mean.dtype == torch.float32 and mean.is_contiguous())
+    _check_gate(ug, p, N, "diffaug_concat_gated")
+    if Cb != 3:
+        raise _lib.HrvError(f"diffaug_concat_gated: the image has {Cb} channels; the kernel serves the PatchGAN shape (3)")
+    with _Timed("layout", "diffaug_concat_gated", 0.0, 4.0 * N * H * W * (a.C + Cb + out.cstride)):
+        _lib.check(lib.hrv_diffaug_concat_gated_f32(a.t.data_ptr(), a.C, a.cstride, b.data_ptr(), u.data_ptr(),
+                                                    None if mean is None else mean.data_ptr(), policy, N, H, W, out.t.data_ptr(),
+                                                    out.cstride, ug.data_ptr(), p.data_ptr(), _stream()), "hrv_diffaug_concat_gated_f32")
+
+
+def diffaug_gsum_gated(g: Act, Ca: int, u: torch.Tensor, policy: int, ug: torch.Tensor, p: torch.Tensor) -> torch.Tensor:
+    """``diffaug_gsum`` under the gates -- hrv_diffaug_gsum_gated_f32."""
+    lib = _lib.load()
+    assert not g.bf16 and g.coff == 0 and g.t.is_contiguous() and tuple(u.shape) == (g.N, 8) and u.is_contiguous()
+    _check_gate(ug, p, g.N, "diffaug_gsum_gated")
+    part, out = _diffaug_part(g.N, g.t.device), torch.empty(g.N, dtype=torch.float64, device=g.t.device)
+    with _Timed("layout", "diffaug_gsum_gated", 0.0, 4.0 * g.N * g.H * g.W * 3):
+        _lib.check(lib.hrv_diffaug_gsum_gated_f32(g.t.data_ptr(), g.cstride, Ca, u.data_ptr(), policy, g.N, g.H, g.W, part.data_ptr(),
+                                                  out.data_ptr(), ug.data_ptr(), p.data_ptr(), _stream()), "hrv_diffaug_gsum_gated_f32")
+    return out
+
+
+def diffaug_bwd_gated(g: Act, Ca: int, u: torch.Tensor, gsum: Optional[torch.Tensor], policy: int, ug: torch.Tensor,
+                      p: torch.Tensor) -> torch.Tensor:
+    """``diffaug_bwd`` under the gates -- hrv_diffaug_bwd_gated_f32."""
+    lib = _lib.load()
+    assert not g.bf16 and g.coff == 0 and g.t.is_contiguous() and tuple(u.shape) == (g.N, 8) and u.is_contiguous()
+    assert gsum is None or (gsum.numel() == g.N and gsum.dtype == torch.float64)
+    _check_gate(ug, p, g.N, "diffaug_bwd_gated")
+    out = torch.empty((g.N, 3, g.H, g.W), dtype=torch.float32, device=g.t.device)
+    with _Timed("layout", "diffaug_bwd_gated", 0.0, 4.0 * out.numel() + ops.act_bytes(g, 3)):
+        _lib.check(lib.hrv_diffaug_bwd_gated_f32(g.t.data_ptr(), g.cstride, Ca, u.data_ptr(), None if gsum is None else gsum.data_ptr(),
+                                                 policy, g.N, g.H, g.W, out.data_ptr(), ug.data_ptr(), p.data_ptr(), _stream()),
+                   "hrv_diffaug_bwd_gated_f32")
+    return out
+
+
+def ada_update(record: torch.Tensor, num_d: int, target: float, step: float, interval: int, p_max: float, state: torch.Tensor):
+    """The controller of the gates' probability: one launch after ``dhead_forward`` of the D step, reading that head's record and
+    advancing ``state`` (fp64 [HRV_ADA_WORDS]) in place -- hrv_ada_update_f64 (the arithmetic is spelled out in the header)."""
+    lib = _lib.load()
+    if record.dtype != torch.float64 or record.numel() != _lib.DHEAD_WORDS or state.dtype != torch.float64 or \
+            state.numel() != _lib.ADA_WORDS or not state.is_contiguous() or not record.is_contiguous() or not state.is_cuda or \
+            state.device != record.device:
+        raise ops.HrvError(f"ada_update: the loss head's record ({_lib.DHEAD_WORDS} float64) and the state ({_lib.ADA_WORDS} float64) "
+                           "live on one GPU")
+    with _Timed("dhead", "ada_update", 0.0, 8.0 * (_lib.ADA_WORDS + 8), "ada_update_kernel"):
+        _lib.check(lib.hrv_ada_update_f64(record.data_ptr(), int(num_d), float(target), float(step), int(interval), float(p_max),
+                                          state.data_ptr(), _stream()), "hrv_ada_update_f64")
+
+
 # ---- fused loss head of the PatchGAN's discriminator step (csrc/dhead.hip; record layout: include/hrviton_hip.h) ----
 def _dhead_desc(x_fake: Sequence[torch.Tensor], x_real: Sequence[torch.Tensor], what: str):
     k = len(x_fake)

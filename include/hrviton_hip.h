@@ -680,6 +680,44 @@ int hrv_diffaug_gsum_f32(const float* g, int32_t g_cstride, int32_t Ca, const fl
 /* d_img fp32 NCHW [N,3,H,W], every element written; gsum fp64 [N] (may be NULL without HRV_DIFFAUG_COLOR) */
 int hrv_diffaug_bwd_f32(const float* g, int32_t g_cstride, int32_t Ca, const float* u, const double* gsum, int32_t policy, int32_t N,
                         int32_t H, int32_t W, float* d_img, hrv_stream_t stream);
+/* The gated twins (adaptive discriminator augmentation, Karras et al. 2020): the signature of the ungated sibling plus
+ *   ug  device fp32 [N][4], uniforms in [0, 1): column 0 gates color, 1 translation, 2 cutout; column 3 is spare and never read
+ *   p   device, ONE fp64 (8-byte aligned), read by the kernel: no host copy, so a controller on the device may move it
+ * Sample n runs everything above under its effective policy
+ *   policy & (((double)ug[n][0] < p[0] ? COLOR : 0) | ((double)ug[n][1] < p[0] ? TRANSLATION : 0) | ((double)ug[n][2] < p[0] ? CUTOUT : 0))
+ * with a strict comparison in fp64: p == 0 applies nothing, p == 1 everything, ug == p does not apply.  A sample whose effective
+ * policy is 0 copies bits in both directions.  The gate is decoded once per block with u's row (the block is the sample).  Color
+ * is gated as one group.  hrv_diffaug_mean_f32 serves both forms; the mean of a sample whose color is gated off is not read. */
+int hrv_diffaug_concat_gated_f32(const float* a, int32_t Ca, int32_t a_cstride, const float* b, const float* u, const float* mean,
+                                 int32_t policy, int32_t N, int32_t H, int32_t W, float* out, int32_t out_cstride, const float* ug,
+                                 const double* p, hrv_stream_t stream);
+int hrv_diffaug_gsum_gated_f32(const float* g, int32_t g_cstride, int32_t Ca, const float* u, int32_t policy, int32_t N, int32_t H,
+                               int32_t W, double* part, double* sum, const float* ug, const double* p, hrv_stream_t stream);
+int hrv_diffaug_bwd_gated_f32(const float* g, int32_t g_cstride, int32_t Ca, const float* u, const double* gsum, int32_t policy,
+                              int32_t N, int32_t H, int32_t W, float* d_img, const float* ug, const double* p, hrv_stream_t stream);
+
+/* The controller of p: one launch of one block after hrv_dhead_forward_f32 of the discriminator step; dhead_record is that head's
+ * record (below), state HRV_ADA_WORDS doubles, zeroed once (P may be preset), every word fp64.  The gates read &state[HRV_ADA_P].
+ * All arithmetic is IEEE fp64 in exactly this order:
+ *   1. STEPS += 1                                            (calls so far, poisoned ones included)
+ *   2. record[HRV_DHEAD_NONFINITE] != 0: return              (a poisoned step is neither accumulated nor counted in the window)
+ *   3. sum = 0; for k = 0 .. num_d - 1 ascending: sum += record[HRV_DHEAD_STATE + HRV_DHEAD_SCALE_WORDS * k + HRV_DHEAD_RT];
+ *      r = sum / (double)num_d
+ *   4. RT_LAST = r; ACC += r; SEEN += 1
+ *   5. SEEN == interval: m = ACC / (double)interval; RT_WINDOW = m; s = (m > target) - (m < target);
+ *      P = min(max(P + s * step, 0), p_max); ACC = SEEN = 0; UPDATES += 1
+ * (s * step is exact, so a fused multiply-add gives the same P.)  target in [-1, 1], step and p_max in [0, 1], interval >= 1.
+ * StyleGAN2-ADA's rule is step = images_per_step * interval / (kimg * 1000) with images_per_step the global batch. */
+#define HRV_ADA_WORDS 8
+#define HRV_ADA_P 0         /* the probability the gates read */
+#define HRV_ADA_ACC 1       /* sum of r over the open window */
+#define HRV_ADA_SEEN 2      /* steps in the open window */
+#define HRV_ADA_UPDATES 3   /* adjustments made so far */
+#define HRV_ADA_RT_WINDOW 4 /* mean r of the last closed window */
+#define HRV_ADA_STEPS 5     /* calls so far */
+#define HRV_ADA_RT_LAST 6   /* r of the last accumulated step */
+int hrv_ada_update_f64(const double* dhead_record, int32_t num_d, double target, double step, int32_t interval, double p_max,
+                       double* state, hrv_stream_t stream);
 
 /* Fused loss head of the PatchGAN's discriminator step: hinge terms, logit statistics, LeCam anchors and regulariser (Tseng et al.,
  * CVPR 2021) and the gradients of all logits, decided ON THE DEVICE (no host read, capturable).  Per scale k < num_d (at most

@@ -32,6 +32,12 @@ on the MI355X-native hot path.
     gradients unchanged) -- hr_viton_amd.lecam.  Anchors, r_t and the count stay on the device; the printed line gains ``D_lecam`` and
     ``r_t``, ``--board`` records ``Loss/dis/lecam`` and ``Reg/*`` per scale, and ``lecam_step_*.pth`` / ``lecam_final.pth`` are
     written beside the discriminator's files (``--lecam_checkpoint FILE`` resumes from one).
+  * ``--ada_target T`` (``--ada_kimg 500 --ada_interval 4 --ada_p_init 0 --ada_p_max 1``) or ``--ada_fixed_p P``, both with ``--diffaug``:
+    adaptive discriminator augmentation (Karras et al. 2020) -- every transform of the policy is applied to a sample with
+    probability p, gated inside the same kernels; with a target, one controller launch per discriminator step moves p on the
+    device so that the windowed r_t of the loss head stays at T (without ``--lecam`` / ``--d_stats`` the head is switched on with
+    weight 0).  The printed line gains ``ada_p``, ``--board`` records ``Aug/p`` and ``Aug/r_t``, and ``ada_step_*.pth`` /
+    ``ada_final.pth`` are written beside the LeCam files (``--ada_checkpoint FILE`` resumes from one).
 Bug-fixes of the reference call sites: tocg(input1, input2) arity, load_checkpoint arity,
 Adam betas as floats.
 """
@@ -52,7 +58,7 @@ import hr_viton_amd  # noqa: E402,F401
 from hr_viton_amd import dist as hdist  # noqa: E402
 from hr_viton_amd import viz  # noqa: E402
 from hr_viton_amd.checkpoint import load_checkpoint, save_checkpoint  # noqa: E402
-from hr_viton_amd.diffaug import add_diffaug_args, diffaug_from_opt  # noqa: E402
+from hr_viton_amd.diffaug import AdaptiveAugment, ada_line, ada_scalars, add_ada_args, add_diffaug_args, diffaug_from_opt  # noqa: E402
 from hr_viton_amd.gen_train import attach_grad_sync  # noqa: E402
 from hr_viton_amd.lecam import add_lecam_args, lecam_from_opt, lecam_line, lecam_scalars  # noqa: E402
 from hr_viton_amd.losses import GANLoss, L1Loss  # noqa: E402
@@ -143,6 +149,7 @@ def get_opt(argv=None):
     add_guard_args(p)
     add_ema_args(p)
     add_diffaug_args(p)
+    add_ada_args(p)
     add_lecam_args(p)
     opt = p.parse_args(argv)
     opt.gpu_ids = [int(s) for s in str(opt.gpu_ids).split(",") if s.strip() and int(s) >= 0]
@@ -183,6 +190,7 @@ class _Validation(object):
         self.opt_g = self.opt_d = None      # the optimizers whose guard records ride along with the loss scalars (main sets them)
         self.ema_eval = False               # --ema_eval: the test passes run on opt_g's averaged weights (main sets it)
         self.lecam = None                   # --lecam / --d_stats: the D step's loss head (main sets it)
+        self.aug = None                     # --ada_target / --ada_fixed_p: the adaptive augmentation (main sets it)
 
     def weights(self):
         """The context the test passes run in: the generator's averaged weights with --ema_eval, the raw ones otherwise."""
@@ -219,6 +227,8 @@ class _Validation(object):
             self.board.add_scalar("Loss/dis/lecam", float(losses["D_LeCam"].mean()), s)
             for tag, val in lecam_scalars(self.lecam):
                 self.board.add_scalar(tag, val, s)
+        for tag, val in ada_scalars(self.aug):                       # (nothing without --ada_target / --ada_fixed_p)
+            self.board.add_scalar(tag, val, s)
         if opt.num_test_visualize > 0:
             vb = self.vis_batch()
             with self.weights():
@@ -319,6 +329,9 @@ def main(argv=None):
         if s is not None:
             attach_grad_sync(s)
     aug = diffaug_from_opt(opt)      # (None without --diffaug: the plain iteration, no new launch)
+    ada = aug if isinstance(aug, AdaptiveAugment) else None      # (None without --ada_target / --ada_fixed_p: nothing allocated)
+    if ada is not None and ada.adaptive and not float(getattr(opt, "lecam", 0.0) or 0.0):
+        opt.d_stats = True           # the controller follows the head's r_t: the head with weight 0
     lecam = lecam_from_opt(opt)      # (None without --lecam / --d_stats: the four GANLoss calls, nothing allocated)
     lam = lambda step: 1.0 - max(0, step * 1000 + opt.load_step - opt.keep_step) / float(opt.decay_step + 1)  # noqa: E731
     sched_g = torch.optim.lr_scheduler.LambdaLR(opt_g, lr_lambda=lam)
@@ -340,6 +353,7 @@ def main(argv=None):
         validation.opt_g, validation.opt_d = opt_g, opt_d
         validation.ema_eval = bool(ema) and bool(getattr(opt, "ema_eval", False))
         validation.lecam = lecam
+        validation.aug = ada
     for step in range(opt.load_step, last):
         t0 = time.time()
         if loader is None:
@@ -363,7 +377,7 @@ def main(argv=None):
             lg = sum(v.item() for k, v in losses.items() if not k.startswith("D_"))
             print("step: %8d, time: %.3f, G_loss: %.4f, G_adv_loss: %.4f, D_loss: %.4f, D_fake_loss: %.4f, D_real_loss: %.4f"
                   % (step + 1, t, lg, losses["GAN"].item(), ld, losses["D_Fake"].item(), losses["D_Real"].item())
-                  + guard_line(opt_g, opt_d) + lecam_line(lecam, losses), flush=True)
+                  + guard_line(opt_g, opt_d) + lecam_line(lecam, losses) + ada_line(ada), flush=True)
         if (step + 1) % opt.save_count == 0 and rank == 0:
             save_checkpoint(generator, os.path.join(opt.checkpoint_dir, opt.name, "gen_step_%06d.pth" % (step + 1)), opt)
             save_checkpoint(discriminator, os.path.join(opt.checkpoint_dir, opt.name, "dis_step_%06d.pth" % (step + 1)), opt)
@@ -372,6 +386,8 @@ def main(argv=None):
                                 state_dict=opt_g.ema_state_dict(generator))
             if lecam is not None:
                 torch.save(lecam.state_dict(), os.path.join(opt.checkpoint_dir, opt.name, "lecam_step_%06d.pth" % (step + 1)))
+            if ada is not None:
+                torch.save(ada.state_dict(), os.path.join(opt.checkpoint_dir, opt.name, "ada_step_%06d.pth" % (step + 1)))
         if (step + 1) % 1000 == 0:
             sched_g.step()
             sched_d.step()
@@ -383,6 +399,8 @@ def main(argv=None):
                             state_dict=opt_g.ema_state_dict(generator))
         if lecam is not None:
             torch.save(lecam.state_dict(), os.path.join(opt.checkpoint_dir, opt.name, "lecam_final.pth"))
+        if ada is not None:
+            torch.save(ada.state_dict(), os.path.join(opt.checkpoint_dir, opt.name, "ada_final.pth"))
         validation.board.close()
         print("Finished training %s!" % opt.name)
 
