@@ -840,6 +840,8 @@ def maxpool2x2(x: Act) -> Act:
 
 def maxpool2x2_bwd(x: Act, dy: Act, relu: bool = False) -> Act:
     """``relu``: x = ReLU(pre) -- the result is the gradient w.r.t. pre (the ReLU derivative rides along)."""
+    # (the entry points take x.Cp as the channel stride of x, dy and dx alike)
+    assert x.coff == 0 and x.cstride == x.Cp and dy.coff == 0 and dy.cstride == dy.Cp, "maxpool2x2_bwd: x and dy must be dense"
     lib = _lib.load()
     dx = ops.alloc(x.N, x.H, x.W, x.C, x.t.device, bf16=dy.bf16)
     assert (relu or not x.bf16) and (not dy.bf16 or (x.bf16 and relu)), \
