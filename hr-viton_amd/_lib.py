@@ -264,6 +264,9 @@ SYMBOLS = {
     "hrv_adam_guarded_ema_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i32, _f, _vp, _f, _i32, _vp]),
     "hrv_adam_dev_guarded_ema_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _f, _f, _f, _f, _f, _vp, _f, _i32, _vp, _vp]),
     "hrv_swap_f32": (C.c_int, [_vp, _vp, _i64, _vp]),
+    "hrv_span_stats_piece": (C.c_int, []),
+    "hrv_span_stats_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _f, _f, _vp, _vp]),
+    "hrv_span_stats_finalize": (C.c_int, [_vp, _vp, _i32, _vp, _vp]),
     "hrv_spectral_norm_f32": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _f, _vp, _vp, _vp]),
     "hrv_spectral_norm_bwd_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp]),
     "hrv_spectral_norm_batched_f32": (C.c_int, [_vp, _i32, _i32, _f, _vp, _vp]),

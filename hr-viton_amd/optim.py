@@ -5,6 +5,7 @@ buckets).  LambdaLR and friends work unchanged (it is a torch.optim.Optimizer)."
 from __future__ import annotations
 
 import contextlib
+import os
 
 import torch
 
@@ -108,6 +109,67 @@ class Adam(torch.optim.Optimizer):
         if not st or "guard" not in st:
             return None
         return T.guard_read(st["guard"])
+
+    # ------------------------------------------------------------------ per-parameter statistics
+    def prepare_layer_stats(self):
+        """Build what layer_stats() needs for every parameter group -- the flat buffers if no step has run yet, the piece table,
+        the partials and the records (train_ops.span_stats_alloc) -- so that a later call allocates nothing: call it before
+        capturing ``layer_stats(read=False)`` in a hipGraph.  Nothing is launched."""
+        for gi, group in enumerate(self.param_groups):
+            st = self._flat.get(gi) or self._setup(gi, group)
+            if "span_ws" not in st:
+                st["span_ws"] = T.span_stats_alloc(st["spans"], st["w"].device)
+
+    def layer_stats(self, group: int = 0, read: bool = True):
+        """Per-parameter statistics of one group's flat buffers in two launches on the current stream (csrc/span_stats.hip; read-only:
+        weights, moments and gradients keep their bits, and an optimizer that is never asked allocates and launches nothing for it).
+        Meant for any time after a step(): the flat gradient buffer still holds that step's gradient until the next backward.  One
+        dict per parameter, in the order of the flat buffer:
+          param, numel
+          grad_norm, grad_maxabs      with the data-parallel 1 / world factor step() applies;  grad_nonfinite, grad_zeros (elements == +-0)
+          weight_norm, weight_maxabs, weight_nonfinite
+          update_norm      (lr / bc1) * ||u||, u = m / (sqrt(v) / bc2_sqrt + eps) formed like the Adam kernel forms it from the CURRENT
+                           moments: after an applied step this is ||w_before - w_after||, with or without weight decay or clipping
+          update_ratio     update_norm / weight_norm (None where weight_norm is 0);  update_nonfinite
+        Non-finite elements are counted and left out of norms and maxima.  After a step the guard SKIPPED, ``grad_*`` describe the
+        poisoned gradient and ``update_*`` the stale moments' direction.  On the host-count path a parameter whose own step count
+        differs from the group's (it had no gradient in some iteration) gets None for update_norm and update_ratio.  Inside
+        ``swap_ema()`` the flat weight buffer holds the averaged weights: ``weight_*`` and ``update_ratio`` then describe those.
+        Reading costs at most two device-to-host copies (the records; on the device-step path lr and the bias corrections).
+        ``read=False``: only the two launches; returns the device record tensor (int32 [n][16]; layout: include/hrviton_hip.h)
+        for a captured iteration -- after prepare_layer_stats() it allocates nothing.  Capture it with ``device_step=True``: the
+        kernel then reads the bias correction from the device; on the host-count path the scalar of the capture would be replayed."""
+        import numpy as np
+        grp = self.param_groups[group]
+        st = self._flat.get(group)
+        if st is None or "span_ws" not in st:
+            self.prepare_layer_stats()
+            st = self._flat[group]
+        b1, b2 = grp["betas"]
+        hyper = st.get("hyper")
+        t = max(int(st["step"]), 1)
+        bc2_sqrt = float(np.sqrt(np.float32(1.0) - np.power(np.float32(b2), np.float32(t))))
+        rec = T.span_stats(st["span_ws"], st["g"], st["w"], st["m"], st["v"], hyper, bc2_sqrt, grp["eps"])
+        if not read:
+            return rec
+        rows = T.span_stats_read(rec)
+        if hyper is not None:
+            lr, bc1 = (float(x) for x in hyper[:2].tolist())
+        else:
+            lr, bc1 = float(grp["lr"]), 1.0 - b1 ** t
+        step_size = lr / bc1 if bc1 != 0.0 else 0.0      # (a device count that never advanced: every step so far was skipped)
+        gscale = 1.0 / self.grad_sync.world if self.grad_sync is not None else 1.0
+        out = []
+        for i, ((p, _, k), r) in enumerate(zip(st["spans"], rows)):
+            wn = r["w_sumsq"] ** 0.5
+            un = step_size * r["u_sumsq"] ** 0.5
+            if hyper is None and st["steps"][i] != st["step"]:
+                un = None
+            out.append({"param": p, "numel": k, "grad_norm": gscale * r["g_sumsq"] ** 0.5, "grad_maxabs": gscale * r["g_maxabs"],
+                        "grad_nonfinite": r["g_nonfinite"], "grad_zeros": r["g_zeros"], "weight_norm": wn,
+                        "weight_maxabs": r["w_maxabs"], "weight_nonfinite": r["w_nonfinite"], "update_norm": un,
+                        "update_ratio": un / wn if un is not None and wn > 0.0 else None, "update_nonfinite": r["u_nonfinite"]})
+        return out
 
     def push_lr(self):
         """device_step: copy each group's current learning rate to its device scalar (call BEFORE replaying a captured
@@ -482,3 +544,108 @@ def guard_line(opt_g, opt_d):
         return ""
     return ", gnorm_G: %.4g, gnorm_D: %.4g, skipped_G: %d, skipped_D: %d" % (sc["Grad/norm_G"], sc["Grad/norm_D"],
                                                                              sc["Grad/skipped_G"], sc["Grad/skipped_D"])
+
+
+# ------------------------------------------------------------------ per-parameter reports (Adam.layer_stats) and the scripts' side of them
+LAYER_FIELDS = ("numel", "grad_norm", "grad_maxabs", "grad_nonfinite", "grad_zeros", "weight_norm", "weight_maxabs", "weight_nonfinite",
+                "update_norm", "update_ratio", "update_nonfinite")
+
+
+def layer_report(opt, module):
+    """{name: Adam.layer_stats() entry without "param"} over every parameter group of ``opt``, keyed by ``module.named_parameters()``
+    names in the order of the flat buffers (a spectral-norm weight reports under ``weight_orig``, as in the state dict).  A
+    parameter of the optimizer that ``module`` does not own is left out."""
+    names = {id(p): n for n, p in module.named_parameters()}
+    out = {}
+    for gi in range(len(opt.param_groups)):
+        for e in opt.layer_stats(gi):
+            name = names.get(id(e["param"]))
+            if name is not None:
+                out[name] = {k: e[k] for k in LAYER_FIELDS}
+    return out
+
+
+def add_layer_stats_args(parser):
+    """--layer_stats_count / --layer_stats_top / --layer_stats_on_skip of train_generator.py and train_condition.py.  Like the
+    guard's flags they appear in the parsed namespace only when given."""
+    import argparse
+    parser.add_argument("--layer_stats_count", type=int, default=argparse.SUPPRESS,
+                        help="every N steps, after both optimizers have stepped, append one per-parameter report per optimizer "
+                             "(gradient, weight and update norms, maxima, non-finite and zero counts; two launches and one small "
+                             "copy each) to <tensorboard_dir>/<name>/layer_stats.jsonl (0: off)")
+    parser.add_argument("--layer_stats_top", type=int, default=argparse.SUPPRESS,
+                        help="how many parameters, by gradient norm, the printed line names per optimizer (default 5)")
+    parser.add_argument("--layer_stats_on_skip", action="store_true", default=argparse.SUPPRESS,
+                        help="needs --skip_nonfinite: write and print the report of an optimizer right after a step its guard "
+                             "skipped, while the flat gradient buffer still holds the poisoned gradient.  Reads the guard record "
+                             "after EVERY step: one host synchronisation per step and optimizer")
+
+
+class LayerStatsLog:
+    """The scripts' per-parameter reports: ``after_step`` writes the due ones and returns the text the printed line gains."""
+
+    def __init__(self, path, count, top, on_skip, pairs):
+        self.path, self.count, self.top, self.on_skip = path, int(count), int(top), bool(on_skip)
+        self.pairs = pairs          # [(tag "G" / "D", optimizer, module)]
+
+    def _text(self, tag, params):
+        by_norm = sorted(params, key=lambda n: -params[n]["grad_norm"])[:self.top]
+        bad = [n for n in params if params[n]["grad_nonfinite"] or params[n]["weight_nonfinite"] or params[n]["update_nonfinite"]]
+        txt = ", layers_%s: " % tag + " ".join("%s=%.4g" % (n, params[n]["grad_norm"]) for n in by_norm)
+        if bad:
+            txt += ", nonfinite_%s: " % tag + " ".join(
+                "%s(g%d/w%d/u%d)" % (n, params[n]["grad_nonfinite"], params[n]["weight_nonfinite"], params[n]["update_nonfinite"])
+                for n in bad)
+        return txt
+
+    def _write(self, step, tag, o, module, board):
+        import json
+        params = layer_report(o, module)
+        os.makedirs(os.path.dirname(self.path), exist_ok=True)
+        with open(self.path, "a") as f:
+            f.write(json.dumps({"step": step, "opt": tag, "params": params}) + "\n")
+        if board is not None:
+            ratios = [e["update_ratio"] for e in params.values() if e["update_ratio"] is not None]
+            board.add_scalar("Layers/%s/update_ratio_max" % tag, max(ratios) if ratios else 0.0, step)
+            board.add_scalar("Layers/%s/update_ratio_min" % tag, min(ratios) if ratios else 0.0, step)
+            board.add_scalar("Layers/%s/nonfinite_params" % tag, float(sum(
+                1 for e in params.values() if e["grad_nonfinite"] or e["weight_nonfinite"] or e["update_nonfinite"])), step)
+            board.add_scalar("Layers/%s/zero_grad_params" % tag, float(sum(1 for e in params.values() if e["grad_zeros"] == e["numel"])), step)
+        return self._text(tag, params)
+
+    def after_step(self, step, board=None):
+        """``step``: the 1-based count of the iteration that just ran.  Returns '' when no report was due."""
+        due = self.count > 0 and step % self.count == 0
+        text = ""
+        for tag, o, module in self.pairs:
+            skipped = False
+            if self.on_skip:
+                gs = o.guard_stats()      # (the host synchronisation --layer_stats_on_skip costs)
+                skipped = gs is not None and gs["apply"] == 0
+            if due or skipped:
+                t = self._write(step, tag, o, module, board)
+                if skipped:
+                    print("step: %8d, optimizer %s skipped its step%s" % (step, tag, t), flush=True)
+                text += t
+        return text
+
+
+def check_layer_stats_args(opt):
+    """(count, on_skip) of the parsed flags; exits with a message on a combination that cannot work (the scripts call it before
+    they build anything)."""
+    count = int(getattr(opt, "layer_stats_count", 0) or 0)
+    on_skip = bool(getattr(opt, "layer_stats_on_skip", False))
+    if on_skip and not getattr(opt, "skip_nonfinite", False):
+        raise SystemExit("--layer_stats_on_skip needs --skip_nonfinite (without it no step is ever skipped)")
+    if count < 0 or int(getattr(opt, "layer_stats_top", 5)) < 0:
+        raise SystemExit("--layer_stats_count and --layer_stats_top must be >= 0")
+    return count, on_skip
+
+
+def layer_stats_from_opt(opt, pairs):
+    """The scripts' LayerStatsLog, or None without --layer_stats_count / --layer_stats_on_skip (nothing is allocated or launched)."""
+    count, on_skip = check_layer_stats_args(opt)
+    if count == 0 and not on_skip:
+        return None
+    return LayerStatsLog(os.path.join(opt.tensorboard_dir, opt.name, "layer_stats.jsonl"), count,
+                         int(getattr(opt, "layer_stats_top", 5)), on_skip, pairs)

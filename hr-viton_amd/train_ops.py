@@ -1027,6 +1027,88 @@ def swap_(a: torch.Tensor, b: torch.Tensor):
         _lib.check(lib.hrv_swap_f32(a.data_ptr(), b.data_ptr(), a.numel(), _stream()), "hrv_swap_f32")
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# Per-parameter statistics of flat buffers (csrc/span_stats.hip): a segmented reduction, read-only, two launches.  A span record
+# is SPAN_WORDS int32 words (layout: include/hrviton_hip.h); span_stats_read() decodes a host copy of all of them.
+# ---------------------------------------------------------------------------------------------------------------
+SPAN_G_SUMSQ, SPAN_W_SUMSQ, SPAN_U_SUMSQ, SPAN_G_MAXABS, SPAN_W_MAXABS, SPAN_U_MAXABS = 0, 2, 4, 6, 7, 8
+SPAN_G_NONFINITE, SPAN_W_NONFINITE, SPAN_U_NONFINITE, SPAN_G_ZEROS = 9, 10, 11, 12
+SPAN_WORDS = 16
+
+
+def span_stats_piece() -> int:
+    return int(_lib.load().hrv_span_stats_piece())
+
+
+def span_pieces(spans, piece: int):
+    """Pure Python: cut every span into pieces of at most ``piece`` elements.  ``spans``: (offset, length) pairs, or the
+    (parameter, offset, length) triples of optim.Adam; every length >= 1.  Returns (pieces, span_first): pieces[p] = (first element,
+    length in 1 .. piece), none crossing a span, the pieces of a span consecutive and in order; span s owns
+    pieces[span_first[s]:span_first[s + 1]] (len(span_first) == len(spans) + 1)."""
+    if piece < 1:
+        raise ValueError(f"span_pieces: piece must be positive, got {piece}")
+    pieces, first = [], [0]
+    for sp in spans:
+        off, k = int(sp[-2]), int(sp[-1])
+        if off < 0 or k < 1:
+            raise ValueError(f"span_pieces: a span needs offset >= 0 and length >= 1, got ({off}, {k})")
+        for a in range(0, k, piece):
+            pieces.append((off + a, min(piece, k - a)))
+        first.append(len(pieces))
+    return pieces, first
+
+
+def span_stats_alloc(spans, device) -> dict:
+    """Everything one flat buffer's reports need, built ONCE (the spans are fixed): the piece table and ``span_first`` on the
+    device, the per-piece partials and the records (int32 [n_spans][SPAN_WORDS]).  ``extent``: one past the last element any piece
+    reads -- span_stats() checks every array against it before it launches."""
+    pieces, first = span_pieces(spans, span_stats_piece())
+    if not pieces:
+        raise ops.HrvError("span_stats_alloc: no spans")
+    return {"pieces": torch.tensor(pieces, dtype=torch.int64).to(device), "span_first": torch.tensor(first, dtype=torch.int32).to(device),
+            "part": torch.zeros(len(pieces), SPAN_WORDS, dtype=torch.int32, device=device),
+            "records": torch.zeros(len(first) - 1, SPAN_WORDS, dtype=torch.int32, device=device),
+            "n_pieces": len(pieces), "n_spans": len(first) - 1, "extent": max(a + k for a, k in pieces)}
+
+
+def span_stats(ws: dict, g: torch.Tensor, w: torch.Tensor, m: Optional[torch.Tensor] = None, v: Optional[torch.Tensor] = None,
+               hyper: Optional[torch.Tensor] = None, bc2_sqrt: float = 1.0, eps: float = 0.0) -> torch.Tensor:
+    """The two launches over workspace ``ws`` (span_stats_alloc); returns ws["records"], still on the device.  ``m`` / ``v``: both
+    or neither (without them the update fields are 0).  ``hyper``: the device-step triple whose [2] is sqrt(1 - beta2^t); it
+    replaces ``bc2_sqrt``.  Nothing is allocated and nothing is read back: capturable."""
+    lib = _lib.load()
+    if (m is None) != (v is None):
+        raise ops.HrvError("span_stats: pass both moments or neither")
+    for name, t in (("g", g), ("w", w), ("m", m), ("v", v)):
+        if t is None:
+            continue
+        ops.require_cuda(t, f"span_stats({name})")
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < ws["extent"]:
+            raise ops.HrvError(f"span_stats: {name} must be a contiguous fp32 buffer of at least {ws['extent']} elements")
+    if hyper is not None and (hyper.dtype != torch.float32 or hyper.numel() < 3 or not hyper.is_cuda):
+        raise ops.HrvError("span_stats: hyper is the device-side float triple (lr, 1 - beta1^t, sqrt(1 - beta2^t))")
+    n_arr = 2 if m is None else 4
+    with _Timed("span_stats", "span_stats_f32", 0.0, 4.0 * n_arr * ws["extent"]):
+        _lib.check(lib.hrv_span_stats_f32(g.data_ptr(), w.data_ptr(), m.data_ptr() if m is not None else None,
+                                          v.data_ptr() if v is not None else None, ws["pieces"].data_ptr(), ws["n_pieces"],
+                                          hyper.data_ptr() if hyper is not None else None, float(bc2_sqrt), float(eps),
+                                          ws["part"].data_ptr(), _stream()), "hrv_span_stats_f32")
+    _lib.check(lib.hrv_span_stats_finalize(ws["part"].data_ptr(), ws["span_first"].data_ptr(), ws["n_spans"],
+                                           ws["records"].data_ptr(), _stream()), "hrv_span_stats_finalize")
+    return ws["records"]
+
+
+def span_stats_read(records: torch.Tensor) -> list:
+    """The span records as Python numbers, one dict per span (ONE device-to-host copy)."""
+    h = records.detach().reshape(-1, SPAN_WORDS).cpu()
+    f, d = h.view(torch.float32).tolist(), h.view(torch.float64).tolist()
+    i = h.tolist()
+    return [{"g_sumsq": d[s][SPAN_G_SUMSQ // 2], "w_sumsq": d[s][SPAN_W_SUMSQ // 2], "u_sumsq": d[s][SPAN_U_SUMSQ // 2],
+             "g_maxabs": f[s][SPAN_G_MAXABS], "w_maxabs": f[s][SPAN_W_MAXABS], "u_maxabs": f[s][SPAN_U_MAXABS],
+             "g_nonfinite": i[s][SPAN_G_NONFINITE], "w_nonfinite": i[s][SPAN_W_NONFINITE], "u_nonfinite": i[s][SPAN_U_NONFINITE],
+             "g_zeros": i[s][SPAN_G_ZEROS]} for s in range(h.shape[0])]
+
+
 def spectral_sigma(w_orig: torch.Tensor, u: torch.Tensor, v: torch.Tensor, power_iterations: int,
                    eps: float = 1e-12) -> torch.Tensor:
     """In-place power iteration on (u, v) + sigma (device scalar tensor [1])."""

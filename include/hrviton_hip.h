@@ -475,6 +475,44 @@ int hrv_adam_dev_guarded_ema_f32(float* w, const float* g, float* m, float* v, f
                                  float beta1, float beta2, float eps, float weight_decay, float grad_scale, const int32_t* record,
                                  float decay, int32_t warmup, const int32_t* step_dev, hrv_stream_t stream);
 int hrv_swap_f32(float* a, float* b, int64_t n, hrv_stream_t stream);
+/* Per-parameter statistics of an optimizer's flat buffers: one segmented reduction, read-only, two launches, no host read, no
+ * atomics (capturable).  A span is one parameter's run of elements; the caller cuts every span into PIECES of at most
+ * hrv_span_stats_piece() elements (a compile-time constant of the library), no piece crossing a span, a span's pieces consecutive.
+ *
+ * hrv_span_stats_f32: pieces[p] = {first element, length in 1 .. PIECE} (device memory, 8-byte aligned).  One block per piece reads
+ * g, w and, where given, m and v (both or neither) over exactly the piece's elements -- nothing outside a piece is read -- and
+ * writes part[p], HRV_SPAN_WORDS words laid out like a record, with plain stores.  Any 4-byte-aligned base pointers, any offsets:
+ * where all arrays read share the position of a piece's first element inside 16 bytes a thread moves 16 bytes of each per trip
+ * between a scalar head and tail, otherwise the piece is read element by element.  Per element, x standing for g, w and u:
+ *   non-finite (exponent field all ones): counted and LEFT OUT of sum and maximum; finite: sumsq += (double)x * (double)x,
+ *   maxabs = max(maxabs, fabsf(x)); for g, elements equal to +-0 are counted as well
+ *   u = m / (sqrtf(v) / bc2_sqrt + eps) in fp32, every operation rounded on its own: the direction of the Adam update the moments
+ *   stand for (hrv_adam_f32 forms mi / denom like this); an element whose m, v or u is non-finite counts in u_nonfinite
+ *   bc2_sqrt is hyper_dev[2] where hyper_dev is given (hrv_adam_hyper_f32's output), else the scalar argument
+ * The piece table alone decides every summation order (per thread over its trips in turn, then its head and tail elements, a
+ * 64-lane shuffle tree, the block's waves in order): the same buffers give the same bits in every run, on every card and grid.
+ *
+ * hrv_span_stats_finalize: span s owns part[span_first[s] .. span_first[s + 1]); one wave per span adds them (lane l the
+ * partials l, l + 64, ... in turn, then the shuffle tree) and writes records[s], HRV_SPAN_WORDS 32-bit words:
+ *   [HRV_SPAN_G_SUMSQ, +1] f64   [HRV_SPAN_W_SUMSQ, +1] f64   [HRV_SPAN_U_SUMSQ, +1] f64 (0 without m / v)      un-scaled
+ *   [HRV_SPAN_G_MAXABS] f32      [HRV_SPAN_W_MAXABS] f32      [HRV_SPAN_U_MAXABS] f32
+ *   [HRV_SPAN_G_NONFINITE] i32   [HRV_SPAN_W_NONFINITE] i32   [HRV_SPAN_U_NONFINITE] i32   [HRV_SPAN_G_ZEROS] i32
+ *   [13 .. 15] reserved, 0 */
+#define HRV_SPAN_G_SUMSQ 0
+#define HRV_SPAN_W_SUMSQ 2
+#define HRV_SPAN_U_SUMSQ 4
+#define HRV_SPAN_G_MAXABS 6
+#define HRV_SPAN_W_MAXABS 7
+#define HRV_SPAN_U_MAXABS 8
+#define HRV_SPAN_G_NONFINITE 9
+#define HRV_SPAN_W_NONFINITE 10
+#define HRV_SPAN_U_NONFINITE 11
+#define HRV_SPAN_G_ZEROS 12
+#define HRV_SPAN_WORDS 16
+int hrv_span_stats_piece(void);
+int hrv_span_stats_f32(const float* g, const float* w, const float* m, const float* v, const int64_t* pieces, int32_t n_pieces,
+                       const float* hyper_dev, float bc2_sqrt, float eps, void* part, hrv_stream_t stream);
+int hrv_span_stats_finalize(const void* part, const int32_t* span_first, int32_t n_spans, int32_t* records, hrv_stream_t stream);
 /* torch spectral_norm (SpectralNorm.compute_weight): `power_iterations` rounds of
  * v<-normalize(W^T u), u<-normalize(W v) in place (eps 1e-12), then sigma = u.(W v).
  * W is [R][K] = weight_orig.reshape(Cout,-1); wv_scratch holds R floats.

@@ -24,6 +24,8 @@ kernels (hr_viton_amd.cond_train, .functional, .losses, .vgg); one iteration is
     is out of scope.
   * --warp_feature encoder / --out_layer conv (networks.py:46-61,142-144) and --upsample nearest (the inter-flow loss's flow
     resize, train_condition.py:242 -- the only place the reference's scripts use the flag) are on the HIP path (round 5).
+  * ``--layer_stats_count N`` (default 0 = off; ``--layer_stats_top 5``, ``--layer_stats_on_skip`` with ``--skip_nonfinite``): per-parameter
+    reports of both optimizers in ``<tensorboard_dir>/<name>/layer_stats.jsonl``, as in train_generator.py (hr_viton_amd.optim).
 """
 import argparse
 import os
@@ -44,7 +46,8 @@ from hr_viton_amd.gen_train import attach_grad_sync  # noqa: E402
 from hr_viton_amd.losses import L1Loss  # noqa: E402
 from hr_viton_amd.networks import (ConditionGenerator, GANLoss, VGGLoss, define_D, load_checkpoint,  # noqa: E402
                                    save_checkpoint)
-from hr_viton_amd.optim import Adam, add_guard_args, guard_kwargs, guard_line, guard_scalars  # noqa: E402
+from hr_viton_amd.optim import (Adam, add_guard_args, add_layer_stats_args, check_layer_stats_args, guard_kwargs, guard_line,  # noqa: E402
+                                guard_scalars, layer_stats_from_opt)
 from hr_viton_amd.parallel import broadcast_module  # noqa: E402
 from hr_viton_amd.pipeline import condition_train_step  # noqa: E402
 from hr_viton_amd.validate import condition_validation_iou, val_items_loader, validation_due  # noqa: E402
@@ -114,6 +117,7 @@ def get_opt(argv=None):
     p.add_argument("--board", action="store_true",
                    help="every --tensorboard_count steps record the loss scalars and the image grids (train_condition.py:362-436)")
     add_guard_args(p)
+    add_layer_stats_args(p)
     opt = p.parse_args(argv)
     return opt
 
@@ -226,6 +230,7 @@ class _Validation(object):
 
 def main(argv=None):
     opt = get_opt(argv)
+    check_layer_stats_args(opt)
     rank, local_rank, world = hdist.init_from_env()
     if opt.fp16:
         from hr_viton_amd import train_ops as _T
@@ -279,6 +284,10 @@ def main(argv=None):
     validation = _Validation(opt, dev) if rank == 0 else None
     if validation is not None:
         validation.opt_g, validation.opt_d = opt_g, opt_d
+    # (None without --layer_stats_count / --layer_stats_on_skip: nothing allocated or launched; rank 0 reports)
+    layers = layer_stats_from_opt(opt, [("G", opt_g, tocg), ("D", opt_d, D)])
+    if rank != 0:
+        layers = None
     for step in range(opt.load_step, last):
         t0 = time.time()
         record = opt.board and validation is not None and validation_due(step, opt.tensorboard_count)       # :362
@@ -293,6 +302,7 @@ def main(argv=None):
                 batch["image"] = raw["image"].to(dev)
         aux = {} if record else None
         losses = condition_train_step(opt, tocg, D, crit_l1, crit_vgg, crit_gan, opt_g, opt_d, batch, sync_g, sync_d, aux=aux)
+        layer_text = layers.after_step(step + 1, validation.board if opt.board else None) if layers is not None else ""
         if validation_due(step, opt.val_count) and validation is not None:          # :313-360
             validation.run(tocg, step)
         if record:
@@ -304,7 +314,7 @@ def main(argv=None):
             print("step: %8d, time: %.3f\nloss G: %.4f, L1_cloth loss: %.4f, VGG loss: %.4f, TV loss: %.4f CE: %.4f, "
                   "G GAN: %.4f\nloss D: %.4f, D real: %.4f, D fake: %.4f"
                   % (step + 1, t, f("loss_G"), f("l1"), f("vgg"), f("tv"), f("ce"), f("g_gan"), f("loss_D"), f("d_real"),
-                     f("d_fake")) + guard_line(opt_g, opt_d).replace(", ", "\n", 1), flush=True)
+                     f("d_fake")) + guard_line(opt_g, opt_d).replace(", ", "\n", 1) + layer_text.replace(", ", "\n", 1), flush=True)
         if (step + 1) % opt.save_count == 0 and rank == 0:
             save_checkpoint(tocg, os.path.join(opt.checkpoint_dir, opt.name, "tocg_step_%06d.pth" % (step + 1)), opt)
             save_checkpoint(D, os.path.join(opt.checkpoint_dir, opt.name, "D_step_%06d.pth" % (step + 1)), opt)

@@ -38,6 +38,11 @@ on the MI355X-native hot path.
     device so that the windowed r_t of the loss head stays at T (without ``--lecam`` / ``--d_stats`` the head is switched on with
     weight 0).  The printed line gains ``ada_p``, ``--board`` records ``Aug/p`` and ``Aug/r_t``, and ``ada_step_*.pth`` /
     ``ada_final.pth`` are written beside the LeCam files (``--ada_checkpoint FILE`` resumes from one).
+  * ``--layer_stats_count N`` (default 0 = off; ``--layer_stats_top 5``): every N steps, after both optimizers have stepped, one
+    per-parameter report per optimizer (hr_viton_amd.optim.layer_report: gradient, weight and update norms, maxima, non-finite and
+    zero counts; two launches and one small copy) is appended to ``<tensorboard_dir>/<name>/layer_stats.jsonl``; the printed line
+    names the top parameters by gradient norm, ``--board`` records ``Layers/{G,D}/*``.  ``--layer_stats_on_skip`` (with
+    ``--skip_nonfinite``) reports right after a skipped step; it reads the guard record after every step, a host synchronisation.
 Bug-fixes of the reference call sites: tocg(input1, input2) arity, load_checkpoint arity,
 Adam betas as floats.
 """
@@ -64,7 +69,8 @@ from hr_viton_amd.lecam import add_lecam_args, lecam_from_opt, lecam_line, lecam
 from hr_viton_amd.losses import GANLoss, L1Loss  # noqa: E402
 from hr_viton_amd.network_generator import MultiscaleDiscriminator, SPADEGenerator  # noqa: E402
 from hr_viton_amd.networks import ConditionGenerator  # noqa: E402
-from hr_viton_amd.optim import Adam, add_ema_args, add_guard_args, ema_kwargs, guard_kwargs, guard_line, guard_scalars  # noqa: E402
+from hr_viton_amd.optim import (Adam, add_ema_args, add_guard_args, add_layer_stats_args, ema_kwargs, guard_kwargs, guard_line,  # noqa: E402
+                                check_layer_stats_args, guard_scalars, layer_stats_from_opt)
 from hr_viton_amd.parallel import broadcast_module  # noqa: E402
 from hr_viton_amd.pipeline import generator_train_step, make_generator_inputs  # noqa: E402
 from hr_viton_amd.validate import (generator_validation_lpips, load_validation_lpips, val_items_loader,  # noqa: E402
@@ -148,6 +154,7 @@ def get_opt(argv=None):
                    help="every --tensorboard_count steps record the loss scalars and the image grids (train_generator.py:364-478)")
     add_guard_args(p)
     add_ema_args(p)
+    add_layer_stats_args(p)
     add_diffaug_args(p)
     add_ada_args(p)
     add_lecam_args(p)
@@ -266,6 +273,7 @@ class _Validation(object):
 
 def main(argv=None):
     opt = get_opt(argv)
+    check_layer_stats_args(opt)
     rank, local_rank, world = hdist.init_from_env()
     if opt.fp16:
         from hr_viton_amd import train_ops as _T
@@ -354,6 +362,11 @@ def main(argv=None):
         validation.ema_eval = bool(ema) and bool(getattr(opt, "ema_eval", False))
         validation.lecam = lecam
         validation.aug = ada
+    # (None without --layer_stats_count / --layer_stats_on_skip: nothing allocated or launched; rank 0 reports -- the gradient
+    # buffers are the all-reduced ones, every rank would report the same)
+    layers = layer_stats_from_opt(opt, [("G", opt_g, generator), ("D", opt_d, discriminator)])
+    if rank != 0:
+        layers = None
     for step in range(opt.load_step, last):
         t0 = time.time()
         if loader is None:
@@ -366,6 +379,7 @@ def main(argv=None):
         losses, _ = generator_train_step(opt, generator, discriminator, crit_gan, crit_feat, crit_vgg, opt_g, opt_d, x,
                                          parse7, batch["image"], sync_g, sync_d, aux=aux, aug=aug,
                                          **({} if lecam is None else {"lecam": lecam}))
+        layer_text = layers.after_step(step + 1, validation.board if opt.board else None) if layers is not None else ""
         if record:
             validation.record(tocg, generator, step, losses, batch, aux, aux["output"])
         if validation_due(step, opt.lpips_count) and validation is not None:        # :480-584
@@ -377,7 +391,7 @@ def main(argv=None):
             lg = sum(v.item() for k, v in losses.items() if not k.startswith("D_"))
             print("step: %8d, time: %.3f, G_loss: %.4f, G_adv_loss: %.4f, D_loss: %.4f, D_fake_loss: %.4f, D_real_loss: %.4f"
                   % (step + 1, t, lg, losses["GAN"].item(), ld, losses["D_Fake"].item(), losses["D_Real"].item())
-                  + guard_line(opt_g, opt_d) + lecam_line(lecam, losses) + ada_line(ada), flush=True)
+                  + guard_line(opt_g, opt_d) + lecam_line(lecam, losses) + ada_line(ada) + layer_text, flush=True)
         if (step + 1) % opt.save_count == 0 and rank == 0:
             save_checkpoint(generator, os.path.join(opt.checkpoint_dir, opt.name, "gen_step_%06d.pth" % (step + 1)), opt)
             save_checkpoint(discriminator, os.path.join(opt.checkpoint_dir, opt.name, "dis_step_%06d.pth" % (step + 1)), opt)
