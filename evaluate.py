@@ -23,6 +23,11 @@ batches.  Differences from the reference script:
     file the values are written as nan, ``--fid_random_init`` runs on seeded random weights and says so) with torch-fidelity's KID
     subsets (``--kid_subsets`` x ``--kid_subset_size``).  One more line goes to eval.txt.  ``--fid_only`` computes nothing else: no
     pairing, no LPIPS weights, lpips.txt untouched.  The workers only decode for this metric; the 299x299 resize is the input kernel's.
+  * ``--prdc`` adds improved precision / recall (Kynkaanniemi et al. 2019) and density / coverage (Naeem et al. 2020) between the same
+    two image sets on the same features and weights flags as ``--fid`` (``--prdc_k`` neighbours, default 5; hr_viton_amd/manifold.py):
+    they separate the loss of fidelity from the loss of diversity that FID and KID merge.  One more line goes to eval.txt.  With
+    ``--fid`` or ``--fid_only`` the feature banks are computed once and scored by both; ``--fid_only --prdc`` writes the two unpaired
+    lines and nothing paired.
 The reference's quirk of dividing the three averages by the number of ground-truth files is kept, so the numbers stay
 comparable; a note is printed when that count differs from the number of predictions.
 """
@@ -43,6 +48,7 @@ IMAGE_EXT = (".jpg", ".jpeg", ".png", ".bmp", ".webp", ".tif", ".tiff")
 ALEXNET_FILE = "alexnet-owt-7be5be79.pth"
 INCEPTION_FILES = ("inception_v3_google-0cc3c7bd.pth", "inception_v3_google-1a9a5a14.pth")    # torchvision's, newer release first
 FID_INCEPTION_FILE = "pt_inception-2015-12-05-6726825d.pth"                                   # pytorch-fid's / torch-fidelity's
+PRDC_K_MAX = 16                                                                               # the library's hrv_row_kth_max()
 
 
 def _default_alexnet_weights():
@@ -86,6 +92,10 @@ def _parser():
                    help="plumbing only: FID / KID on a randomly initialised network (the output is labelled)")
     p.add_argument("--kid_subsets", type=int, default=100, help="KID subsets (torch-fidelity's default)")
     p.add_argument("--kid_subset_size", type=int, default=1000, help="images per KID subset (torch-fidelity's default)")
+    p.add_argument("--prdc", action="store_true",
+                   help="also score precision / recall / density / coverage between all images of --predict_dir and all of "
+                        "--ground_truth_dir, on the FID network's features (its weights flags apply)")
+    p.add_argument("--prdc_k", type=int, default=5, help="nearest neighbours of --prdc (prdc's default; 1 .. %d)" % PRDC_K_MAX)
     return p
 
 
@@ -102,6 +112,8 @@ def get_opt(argv=None):
         opt.fid_inception_weights = os.path.join(torch.hub.get_dir(), "checkpoints", FID_INCEPTION_FILE)
     if opt.kid_subsets < 1 or opt.kid_subset_size < 2:
         p.error("--kid_subsets must be at least 1 and --kid_subset_size at least 2")
+    if not 1 <= opt.prdc_k <= PRDC_K_MAX:
+        p.error("--prdc_k must lie in 1 .. %d" % PRDC_K_MAX)
     return opt
 
 
@@ -316,12 +328,15 @@ class FidScorer:
     def score(self, bank_pred, bank_gt, subsets, subset_size):
         return self.stats.fid_kid(bank_pred, bank_gt, subsets, subset_size)
 
+    def prdc(self, bank_pred, bank_gt, k):
+        """dict(precision, recall, density, coverage, ...): the ground truths are the real bank, the predictions the fake one"""
+        from hr_viton_amd import manifold
+        return manifold.prdc(bank_gt, bank_pred, k)
 
-def fid_evaluation(opt, pred_list, gt_images, fid_scorer):
-    """(fid, kid_mean, kid_std, timings) between all predictions and all ground truths."""
-    t0 = time.perf_counter()
+
+def feature_banks(opt, pred_list, gt_images, fid_scorer):
+    """The two feature banks (predictions, ground truths) of the unpaired metrics, filled batch by batch."""
     banks = []
-    print("Calculate FID, KID...")
     for folder, names, res in ((opt.predict_dir, pred_list, None),
                                (opt.ground_truth_dir, gt_images, opt.resolution if opt.resolution != 1024 else None)):
         loader = torch.utils.data.DataLoader(ImageDataset(folder, names, res), batch_size=max(1, opt.batch_size), shuffle=False,
@@ -331,9 +346,7 @@ def fid_evaluation(opt, pred_list, gt_images, fid_scorer):
             fid_scorer.fill(bank, row, batch)
             row += len(batch)
         banks.append(bank)
-    t1 = time.perf_counter()
-    fid, kid_mean, kid_std = fid_scorer.score(banks[0], banks[1], opt.kid_subsets, opt.kid_subset_size)
-    return float(fid), float(kid_mean), float(kid_std), {"fid_features_s": t1 - t0, "fid_stats_s": time.perf_counter() - t1}
+    return banks
 
 
 def write_fid(predict_dir, fid, kid_mean, kid_std, random_init=False):
@@ -343,30 +356,67 @@ def write_fid(predict_dir, fid, kid_mean, kid_std, random_init=False):
             f.write("FID Inception weights : random init (plumbing only)\n")
 
 
+def write_prdc(predict_dir, precision, recall, density, coverage, k, random_init=False):
+    with open(os.path.join(predict_dir, "eval.txt"), "a") as f:
+        f.write(f"Precision : {precision} / Recall : {recall} / Density : {density} / Coverage : {coverage} / k : {k}\n")
+        if random_init:
+            f.write("FID Inception weights : random init (plumbing only)\n")
+
+
 def run_fid(opt, pred_list, fid_scorer=None):
-    """The --fid / --fid_only part of main(): returns the dict entries and writes eval.txt's extra line."""
+    """The unpaired part of main() -- FID / KID under --fid or --fid_only, precision / recall / density / coverage under --prdc, both
+    on one pair of feature banks: returns the dict entries and the timings and writes eval.txt's extra line(s)."""
+    with_fid, with_prdc = opt.fid or opt.fid_only, opt.prdc
     gt_images = list_predictions(opt.ground_truth_dir)
-    if opt.kid_subset_size > min(len(pred_list), len(gt_images)):
+    if with_fid and opt.kid_subset_size > min(len(pred_list), len(gt_images)):
         _parser().error(f"--kid_subset_size {opt.kid_subset_size} is larger than an image set: {len(pred_list)} predictions in "
+                        f"{opt.predict_dir}, {len(gt_images)} ground truths in {opt.ground_truth_dir}")
+    if with_prdc and opt.prdc_k > min(len(pred_list), len(gt_images)) - 1:
+        _parser().error(f"--prdc_k {opt.prdc_k} is larger than an image set minus one: {len(pred_list)} predictions in "
                         f"{opt.predict_dir}, {len(gt_images)} ground truths in {opt.ground_truth_dir}")
     random_init = fid_scorer is not None and opt.fid_random_init
     if fid_scorer is None:
         model, random_init = load_fid_inception(opt)
         if model is not None:
             fid_scorer = FidScorer(model)
-    timings = {}
+    what = " / ".join(n for n, on in (("FID / KID", with_fid), ("precision / recall / density / coverage", with_prdc)) if on)
+    res, timings, banks = {}, {}, None
     if fid_scorer is None:
-        print("FID / KID: not computed (they need the FID Inception-v3: --fid_inception_weights, now %r, does not exist and nothing "
-              "is downloaded; --fid_random_init for plumbing runs): written as nan" % opt.fid_inception_weights, file=sys.stderr)
-        fid = kid_mean = kid_std = float("nan")
+        print("%s: not computed (they need the FID Inception-v3: --fid_inception_weights, now %r, does not exist and nothing "
+              "is downloaded; --fid_random_init for plumbing runs): written as nan" % (what, opt.fid_inception_weights), file=sys.stderr)
     else:
+        print("Calculate %s..." % ("FID, KID" if with_fid else "precision, recall, density, coverage"))
+        t0 = time.perf_counter()
         with torch.no_grad():
-            fid, kid_mean, kid_std, timings = fid_evaluation(opt, pred_list, gt_images, fid_scorer)
-    write_fid(opt.predict_dir, fid, kid_mean, kid_std, random_init)
-    print("FID : %f / KID_mean : %f / KID_std : %f" % (fid, kid_mean, kid_std))
-    if random_init:
-        print("(FID / KID from randomly initialised weights: plumbing only)")
-    return {"fid": fid, "kid_mean": kid_mean, "kid_std": kid_std, "fid_images": [len(pred_list), len(gt_images)]}, timings
+            banks = feature_banks(opt, pred_list, gt_images, fid_scorer)
+        timings["fid_features_s"] = time.perf_counter() - t0
+    if with_fid:
+        fid = kid_mean = kid_std = float("nan")
+        if banks is not None:
+            t1 = time.perf_counter()
+            with torch.no_grad():
+                fid, kid_mean, kid_std = (float(v) for v in fid_scorer.score(banks[0], banks[1], opt.kid_subsets, opt.kid_subset_size))
+            timings["fid_stats_s"] = time.perf_counter() - t1
+        write_fid(opt.predict_dir, fid, kid_mean, kid_std, random_init)
+        print("FID : %f / KID_mean : %f / KID_std : %f" % (fid, kid_mean, kid_std))
+        if random_init:
+            print("(FID / KID from randomly initialised weights: plumbing only)")
+        res.update({"fid": fid, "kid_mean": kid_mean, "kid_std": kid_std, "fid_images": [len(pred_list), len(gt_images)]})
+    if with_prdc:
+        vals = dict.fromkeys(("precision", "recall", "density", "coverage"), float("nan"))
+        if banks is not None:
+            t1 = time.perf_counter()
+            with torch.no_grad():
+                got = fid_scorer.prdc(banks[0], banks[1], opt.prdc_k)
+            vals = {key: float(got[key]) for key in vals}
+            timings["prdc_s"] = time.perf_counter() - t1
+        write_prdc(opt.predict_dir, vals["precision"], vals["recall"], vals["density"], vals["coverage"], opt.prdc_k, random_init)
+        print("Precision : %f / Recall : %f / Density : %f / Coverage : %f / k : %d"
+              % (vals["precision"], vals["recall"], vals["density"], vals["coverage"], opt.prdc_k))
+        if random_init:
+            print("(precision / recall / density / coverage from randomly initialised weights: plumbing only)")
+        res.update(vals, prdc_k=opt.prdc_k)
+    return res, timings
 
 
 def write_results(predict_dir, lpips_list, avg_ssim, avg_mse, avg_distance, is_mean, is_std, random_init=False,
@@ -473,7 +523,7 @@ def main(argv=None, scorer=None, is_scorer=None, fid_scorer=None):
         print("(Inception Score from randomly initialised weights: plumbing only)")
     res = {"ssim": avg_ssim, "mse": avg_mse, "lpips": avg_distance, "is_mean": is_mean, "is_std": is_std, "pairs": len(pred_list),
            "timings": timings}
-    if opt.fid:
+    if opt.fid or opt.prdc:
         fid_res, fid_timings = run_fid(opt, pred_list, fid_scorer)
         res.update(fid_res)
         timings.update(fid_timings)

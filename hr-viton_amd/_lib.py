@@ -386,6 +386,11 @@ SYMBOLS = {
     "hrv_feat_mean_f64": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
     "hrv_feat_center_t_f64": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp]),
     "hrv_kid_subset_sums_f64": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "hrv_row_sqnorm_f64": (C.c_int, [_vp, _i32, _i32, _i64, _vp, _vp]),
+    "hrv_sqdist_nt_f64": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i64, _i64, _vp, _vp, _i64, _vp, _i64, _vp]),
+    "hrv_row_kth_max": (C.c_int, []),
+    "hrv_row_kth_f64": (C.c_int, [_vp, _i32, _i32, _i64, _i32, _vp, _vp]),
+    "hrv_row_ball_f64": (C.c_int, [_vp, _vp, _i32, _i32, _i64, _vp, _vp, _vp]),
     "hrv_seg_iou_nchw_f32": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "hrv_lpips_prep_resize_nchw_f32": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_float),
                                                  C.POINTER(C.c_float), _vp, _vp]),

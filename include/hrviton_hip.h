@@ -1228,6 +1228,31 @@ int hrv_feat_center_t_f64(const float* x, const double* mean, int32_t n, int32_t
 int hrv_kid_subset_sums_f64(const double* Kxx, int32_t nx, const double* Kyy, int32_t ny, const double* Kxy, const int32_t* ix,
                             const int32_t* iy, int32_t S, int32_t m, double* out, hrv_stream_t stream);
 
+/* ---- nearest-neighbour manifold statistics in float64: precision / recall / density / coverage (manifold.hip) ---- */
+/* All four: no atomics, nothing that depends on the grid, results bit-identical from run to run; null pointers and bad extents
+ * return non-zero before anything is launched. */
+/* out[i] = sum over c < D of (double)x[i][c]^2, i < n: x fp32 [n][ld] (ld >= D), out fp64 [n].  Lane l of the row's wave adds
+ * columns l, l + 64, ... in ascending order; the 64 partial sums meet in a fixed butterfly (32, 16, 8, 4, 2, 1 lanes apart). */
+int hrv_row_sqnorm_f64(const float* x, int32_t n, int32_t D, int64_t ld, double* out, hrv_stream_t stream);
+/* out[i][j] = max(0, (normX[i] + normY[j]) - 2 * sum_c X[i][c] * Y[j][c]), i < nx, j < ny: X fp32 [nx][ldx], Y fp32 [ny][ldy] with c
+ * contiguous (ldx, ldy >= D), normX fp64 [nx], normY fp64 [ny] (hrv_row_sqnorm_f64 of the same rows), out fp64 [nx][ldo] (ldo >= ny).
+ * Products and sums in fp64 on v_mfma_f64_16x16x4_f64 in ascending c, as in hrv_gemm_nt_f64; any nx, ny, D >= 1.  self_offset >= 0
+ * (needs self_offset + nx <= ny): the element j == self_offset + i of every row i is written as +inf -- the row's own entry when X
+ * is the slab of Y that starts at row self_offset.  self_offset == -1: nothing is replaced. */
+int hrv_sqdist_nt_f64(const float* X, const float* Y, int32_t nx, int32_t ny, int32_t D, int64_t ldx, int64_t ldy,
+                      const double* normX, const double* normY, int64_t self_offset, double* out, int64_t ldo, hrv_stream_t stream);
+/* The largest k hrv_row_kth_f64 serves: a compile-time constant of the library, 16. */
+int hrv_row_kth_max(void);
+/* out[i] = the k-th smallest (1-based, counted with multiplicity, so defined regardless of ties) of d[i][0 .. n), i < rows: d fp64
+ * [rows][ld] (ld >= n), out fp64 [rows]; 1 <= k <= min(hrv_row_kth_max(), n).  +inf sorts last: with fewer than k finite entries the
+ * result is +inf.  NaN entries are passed over. */
+int hrv_row_kth_f64(const double* d, int32_t rows, int32_t n, int64_t ld, int32_t k, double* out, hrv_stream_t stream);
+/* cnt[i] (int32) = #{ j < n : d[i][j] < r_col[j] } (strict) and dmin[i] (fp64) = min over j < n of d[i][j], i < rows: d fp64
+ * [rows][ld] (ld >= n), r_col fp64 [n].  Either of cnt, dmin may be NULL (not both).  An integer sum and a minimum: exact in any
+ * order. */
+int hrv_row_ball_f64(const double* d, const double* r_col, int32_t rows, int32_t n, int64_t ld, int32_t* cnt, double* dmin,
+                     hrv_stream_t stream);
+
 /* ---- validation passes of the training scripts (validate.hip) ---- */
 /* The counts behind train_condition.py's iou_metric (:18-36), per sample, in one launch: seg fp32 NCHW [N,13,h,w] (raw logits), cm
  * fp32 [N,1,h,w] (may be NULL when comp == 0), label fp32 NCHW [N,13,h,w] (one-hot).  comp 0: no_composition; 1: detach (channel 3

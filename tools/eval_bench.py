@@ -1,6 +1,6 @@
 """Evaluation micro-benchmark (evaluate.py's GPU work, csrc/metrics.hip + AlexNet on the fp32 conv engine).
 
-  python tools/eval_bench.py [--pairs B] [--reps R] [--e2e N] [--out DIR] [--only viz]
+  python tools/eval_bench.py [--pairs B] [--reps R] [--e2e N] [--out DIR] [--only viz|prdc]
 
 1. pair statistics (gray + SSIM + SSE) on B synthetic device-resident 1024x768 RGB pairs: event time per pair and the fraction
    of the larger of two floors -- bytes (both uint8 images read once, at the measured 6.29 TB/s copy rate) and VALU FLOPs (the
@@ -25,6 +25,11 @@
    byte once) against the copy rate, and the wall time including the uint8 copy to the host -- next to the host path measured in
    the same process: the fp32 panels copied to the host and composed there as the reference does (argmax + PIL palette, make_grid,
    mul(255).add(0.5).clamp).  The same for ``save_images``' quantise-and-copy at 1024x768, batch 16, against the host expression.
+8. precision / recall / density / coverage (``evaluate.py --prdc``, csrc/manifold.hip; ``--only prdc`` runs this section alone and,
+   with ``--out DIR``, writes DIR/prdc_bench.txt): two Gaussian banks of 2032 x 2048 -- each of the four launches (row norms, one
+   2032 x 2032 block of squared distances next to ``poly_gram`` on the same banks, the k-th smallest of its rows, ball counts and
+   minima), the whole of ``manifold.prdc``, and in the same run the same computation written in torch (``torch.cdist`` on fp64
+   copies, ``kthvalue``, compare and sum).
 Event times include launch gaps; for kernel-only times run this under ``rocprofv3 --kernel-trace --stats`` in a run of its own.
 Prints one JSON line.
 """
@@ -252,6 +257,65 @@ def viz_bench(reps, H=1024, W=768):
     return out
 
 
+def _torch_prdc(real, fake, k):
+    """Naeem et al.'s ``prdc`` written in torch on the device: fp64 copies, ``torch.cdist``, ``kthvalue`` (the k + 1-th of a row
+    that holds its own zero), compare and sum."""
+    R, F = real.double(), fake.double()
+    dRR, dFF, dRF = torch.cdist(R, R), torch.cdist(F, F), torch.cdist(R, F)
+    rR, rF = dRR.kthvalue(k + 1, dim=1).values, dFF.kthvalue(k + 1, dim=1).values
+    inside = dRF < rR[:, None]
+    return {"precision": inside.any(dim=0).double().mean().item(), "recall": (dRF < rF[None, :]).any(dim=1).double().mean().item(),
+            "density": inside.sum(dim=0).double().mean().item() / k, "coverage": (dRF.min(dim=1).values < rR).double().mean().item()}
+
+
+def prdc_bench(reps, n=2032, D=2048, k=5):
+    """Section 8.  Returns (dict, text): the four launches of csrc/manifold.hip one by one (event time), the whole of
+    ``manifold.prdc`` and the same computation in torch (host clock around calls that end in a read-back), same run, same GPU."""
+    from hr_viton_amd import feat_stats, manifold
+    g = torch.Generator(device="cuda").manual_seed(5)
+    real = torch.randn(n, D, device="cuda", generator=g)
+    fake = torch.randn(n, D, device="cuda", generator=g) * 1.05 + 0.02
+    r = max(5, reps)
+    nR, nF = manifold.row_sqnorm(real), manifold.row_sqnorm(fake)
+    d_self = manifold.sqdist(real, real, nR, nR, self_offset=0)
+    rR = manifold.row_kth(d_self, k)
+    d = manifold.sqdist(real, fake, nR, nF)
+    t = {"row_sqnorm": timed(lambda: manifold.row_sqnorm(real), r),
+         "sqdist": timed(lambda: manifold.sqdist(real, fake, nR, nF), r),
+         "row_kth": timed(lambda: manifold.row_kth(d_self, k), r),
+         "row_ball": timed(lambda: manifold.row_ball(d, rR), r),
+         "poly_gram": timed(lambda: feat_stats.poly_gram(real, fake), r)}
+    t_hip = _wall(lambda: manifold.prdc(real, fake, k), r)
+    t_torch = _wall(lambda: _torch_prdc(real, fake, k), r)
+    got, ref = manifold.prdc(real, fake, k), _torch_prdc(real, fake, k)
+    flop = 2.0 * n * n * D
+    blk = 8.0 * n * n
+    out = {"n": n, "D": D, "k": k, "reps": r,
+           "row_sqnorm_us": 1e6 * t["row_sqnorm"], "row_sqnorm_gb_per_s": 4.0 * n * D / t["row_sqnorm"] / 1e9,
+           "sqdist_ms": 1e3 * t["sqdist"], "sqdist_tflops_f64": flop / t["sqdist"] / 1e12,
+           "poly_gram_ms": 1e3 * t["poly_gram"], "sqdist_over_poly_gram": t["sqdist"] / t["poly_gram"],
+           "row_kth_us": 1e6 * t["row_kth"], "row_kth_gb_per_s": blk / t["row_kth"] / 1e9,
+           "row_ball_us": 1e6 * t["row_ball"], "row_ball_gb_per_s": blk / t["row_ball"] / 1e9,
+           "prdc_ms": 1e3 * t_hip, "torch_prdc_ms": 1e3 * t_torch, "torch_over_hip": t_torch / t_hip,
+           "prdc": {m: got[m] for m in ("precision", "recall", "density", "coverage")}, "torch_prdc": ref}
+    text = "\n".join([
+        "prdc_bench: %s" % torch.cuda.get_device_name(0),
+        "two Gaussian banks of %d x %d fp32, k = %d; %d repetitions after one warm-up call; event times include launch gaps" % (n, D, k, r),
+        "  row_sqnorm   %9.1f us   (%.0f GB/s of the bank read once)" % (out["row_sqnorm_us"], out["row_sqnorm_gb_per_s"]),
+        "  sqdist       %9.3f ms   (%.1f TFLOP/s fp64 over 2 n^2 D; poly_gram, the same skeleton, same run: %.3f ms, ratio %.2f)"
+        % (out["sqdist_ms"], out["sqdist_tflops_f64"], out["poly_gram_ms"], out["sqdist_over_poly_gram"]),
+        "  row_kth      %9.1f us   (%.0f GB/s of the %d x %d fp64 block read once)" % (out["row_kth_us"], out["row_kth_gb_per_s"], n, n),
+        "  row_ball     %9.1f us   (%.0f GB/s of the block read once)" % (out["row_ball_us"], out["row_ball_gb_per_s"]),
+        "  prdc() whole %9.3f ms   host clock, ends in the read-back of counts and radii (2 norms, 4 distance blocks, 2 row_kth, 2 row_ball)"
+        % out["prdc_ms"],
+        "  torch route  %9.3f ms   host clock: fp64 copies, 3 torch.cdist, 2 kthvalue, compare and sum, 4 .item()" % out["torch_prdc_ms"],
+        "  torch route / prdc(): %.2f" % out["torch_over_hip"],
+        "  prdc()      : " + " / ".join("%s %.6f" % (m, got[m]) for m in ("precision", "recall", "density", "coverage")),
+        "  torch route : " + " / ".join("%s %.6f" % (m, ref[m]) for m in ("precision", "recall", "density", "coverage")),
+    ]) + "\n"
+    return out, text
+
+
 def e2e(n, workers, batch):
     from PIL import Image
     rng = np.random.default_rng(0)
@@ -286,8 +350,17 @@ def main():
     ap.add_argument("--e2e", type=int, default=64, help="pairs of the evaluate.py run (0: skip)")
     ap.add_argument("--workers", type=int, default=8)
     ap.add_argument("--out", default="")
-    ap.add_argument("--only", default="", choices=["", "viz"], help="run one section alone")
+    ap.add_argument("--only", default="", choices=["", "viz", "prdc"], help="run one section alone")
     a = ap.parse_args()
+    if a.only == "prdc":
+        res, text = prdc_bench(a.reps)
+        print(text, end="")
+        print(json.dumps({"prdc": res}))
+        if a.out:
+            os.makedirs(a.out, exist_ok=True)
+            with open(os.path.join(a.out, "prdc_bench.txt"), "w") as f:
+                f.write(text)
+        return
     if a.only == "viz":
         res = {"viz": viz_bench(a.reps)}
         print(json.dumps(res))
@@ -312,7 +385,7 @@ def main():
                           "fraction_of_floor": floor / t_ps},
            "lpips_128": {"B": B, "ms_per_pair": 1e3 * t_lp / B},
            "inception_299": inception_bench(B, a.reps), "validation": validation_bench(B, a.reps), "fid": fid_bench(B, a.reps),
-           "viz": viz_bench(a.reps)}
+           "viz": viz_bench(a.reps), "prdc": prdc_bench(a.reps)[0]}
     if a.e2e:
         res["evaluate_py"] = e2e(a.e2e, a.workers, B)
     print(json.dumps(res))
