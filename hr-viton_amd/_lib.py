@@ -197,6 +197,14 @@ class hrv_viz_panel_t(C.Structure):
                 ("C", C.c_int32), ("kind", C.c_int32)]
 
 
+class hrv_instnorm_jvp_t(C.Structure):
+    _fields_ = ([(k, C.c_void_p) for k in ("x", "mean", "rstd", "f", "t", "df", "cin", "tbar", "cbar", "record", "workspace")] +
+                [(k, C.c_int32) for k in ("N", "H", "W", "C", "x_cstride", "x_coff", "f_cstride", "f_coff", "t_cstride", "t_coff",
+                                          "df_cstride", "df_coff", "cin_cstride", "cin_coff", "tbar_cstride", "tbar_coff",
+                                          "cbar_cstride", "cbar_coff")] +
+                [("slope", C.c_float), ("reserved", C.c_int32)])
+
+
 # every symbol include/hrviton_hip.h declares: (restype, argtypes)
 _i32, _i64, _f, _vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
 _d = C.c_double
@@ -395,6 +403,11 @@ SYMBOLS = {
     "hrv_lpips_prep_resize_nchw_f32": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_float),
                                                  C.POINTER(C.c_float), _vp, _vp]),
     "hrv_viz_grid_u8": (C.c_int, [C.POINTER(hrv_viz_panel_t), _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "hrv_instnorm_jvp_workspace_elems": (_i64, [_i32, _i32, _i32, _i32]),
+    "hrv_instnorm_jvp_stats_nhwc_f32": (C.c_int, [C.POINTER(hrv_instnorm_jvp_t), _vp]),
+    "hrv_instnorm_jvp_bwd_nhwc_f32": (C.c_int, [C.POINTER(hrv_instnorm_jvp_t), _vp]),
+    "hrv_r1_seed_slots": (C.c_int, []),
+    "hrv_r1_seed_nhwc_f32": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _f, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -73,7 +73,7 @@ def make_generator_inputs(opt, tocg, inputs: Dict[str, torch.Tensor], aux: Optio
 
 def generator_train_step(opt, generator, discriminator, crit_gan, crit_feat, crit_vgg, opt_g, opt_d, x, parse7, im,
                          sync_g=None, sync_d=None, noise=None, noise_d=None, aux: Optional[dict] = None, aug=None, aug_u=None,
-                         lecam=None):
+                         lecam=None, r1=None):
     """One G step + one D step of train_generator.py:279-360.  ``parse7``: Act [N,H,W,8] (7 real).  ``aux``: a dictionary that
     receives 'output', the D step's generator output, which is what the reference's recording block shows (:368).
     ``noise`` / ``noise_d``: the SPADE noise draws of the two generator forwards (default: drawn like the reference,
@@ -84,7 +84,9 @@ def generator_train_step(opt, generator, discriminator, crit_gan, crit_feat, cri
     and the regulariser in three launches); ``losses`` gains 'D_LeCam'.  The G step is untouched.  With a diffaug.AdaptiveAugment
     as ``aug`` the assemblies run gated, ``aug_u`` entries are (u, ug) pairs, and -- adaptive form -- one controller launch follows
     the loss head's forward: the D step of iteration t sets the p both discriminator calls of iteration t + 1 see (it needs
-    ``lecam``; a step the gradient guard skips later is not rolled back in the controller)."""
+    ``lecam``; a step the gradient guard skips later is not rolled back in the controller).  ``r1``: an r1.R1 -- behind the D step's
+    ``opt_d.step()`` follow ``opt_d.zero_grad()``, one R1 phase on the un-augmented real images and a second ``opt_d.step()``;
+    ``losses`` gains 'D_R1'.  The caller passes it in the iterations where ``r1.due(step)``; None leaves the function as it is."""
     if lecam is not None and getattr(crit_gan, "gan_mode", None) != "hinge":
         raise ops.HrvError("generator_train_step: the LeCam loss head computes the hinge terms of GANLoss('hinge'); this crit_gan is "
                            "%r" % (getattr(crit_gan, "gan_mode", type(crit_gan).__name__),))
@@ -159,6 +161,12 @@ def generator_train_step(opt, generator, discriminator, crit_gan, crit_feat, cri
     loss_dis.backward()
     opt_d.step()
     losses.update(d_losses)
+    if r1 is not None:      # StyleGAN2's separate Dreg phase: its own gradient, its own optimizer step
+        if sync_d is not None:
+            sync_d.begin()
+        opt_d.zero_grad()
+        losses.update(D_R1=r1.phase(discriminator, parse7, im)["D_R1"])
+        opt_d.step()
     return losses, output_paired
 
 

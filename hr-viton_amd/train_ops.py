@@ -1188,10 +1188,13 @@ def prepare_convs(owner, convs, power_iteration: bool, backward: bool = True, ex
         pb.run(backward)
 
 
-def _prepare_sigmas(owner, convs, power_iteration: bool):
+def spectral_sigmas(owner, convs, power_iteration: bool) -> list:
+    """[(conv, sigma [1], u_keep, v_keep)] of the spectral-normalised convolutions among ``convs`` in one batched run (``owner`` caches
+    the SpectralBatch as ``_sn_batch``).  Nothing is written to the convolutions: with ``power_iteration`` False the module's stored
+    (u, v) keep their bits as well (a reader that must leave the plan alone: r1.R1.phase)."""
     sn = [c for c in convs if c.spectral]
     if not sn:
-        return
+        return []
     batch = getattr(owner, "_sn_batch", None)
     key = tuple(id(c) for c in sn)
     if batch is None or batch[0] != key:
@@ -1202,7 +1205,11 @@ def _prepare_sigmas(owner, convs, power_iteration: bool):
     b = batch[1]
     b.items = [(c.wparam.data, c.conv.weight_u, c.conv.weight_v) for c in sn]     # .data may be re-pointed between steps
     sig, us, vs = b.run(1 if power_iteration else 0)
-    for c, s_, u_, v_ in zip(sn, sig, us, vs):
+    return list(zip(sn, sig, us, vs))
+
+
+def _prepare_sigmas(owner, convs, power_iteration: bool):
+    for c, s_, u_, v_ in spectral_sigmas(owner, convs, power_iteration):
         c.sigma, c.u, c.v = s_, u_, v_
 
 

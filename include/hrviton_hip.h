@@ -1296,6 +1296,53 @@ typedef struct {
 int hrv_viz_grid_u8(const hrv_viz_panel_t* panels, int32_t npanels, int32_t nrow, int32_t padding, int32_t N, int32_t H, int32_t W,
                     int32_t quant, uint8_t* out, hrv_stream_t stream);
 
+/* ---- R1 gradient penalty of the PatchGAN by a tangent pass (r1.py; r1.hip) ----
+ * InstanceNorm + LeakyReLU under a forward-mode tangent, per (sample, channel) over P = H * W pixels:
+ *     y = (x - mean) * rstd;  f = lrelu(y);  tangent t of x:  ydot = rstd * (t - mean_P(t) - y * mean_P(y t));  fdot = lrelu'(y) * ydot
+ * (ydot is what hrv_spade_norm_bwd_nhwc_f32 computes for dout = t without an activation: the Jacobian is symmetric).  The two
+ * launches below are the REVERSE of that pair of maps.  With df the adjoint of fdot and q = lrelu'(f) * df:
+ *     tbar = rstd * (q - mean(q) - y * mean(y q))                                          the adjoint of t
+ *     A = sum(q t) - P mean(q) mean(t);  B = P mean(y q) mean(y t);  w = q mean(y t) + t mean(y q)
+ *     cbar = -(rstd^2 / P) (A - B) y - rstd^2 (w - mean(w) - y mean(y w)) (+ cin)          the tangent path's adjoint of x
+ *     mean(w) = mean(q) mean(y t) + mean(t) mean(y q);  mean(y w) = 2 mean(y q) mean(y t)
+ * hrv_instnorm_jvp_stats_nhwc_f32: record[n][c][0..4] = sum q, sum t, sum y q, sum y t, sum q t (fp64; every product and sum in
+ *   fp64 from the fp32 operands).  Pixel slabs as hrv_instnorm_stats_nhwc_f32 (a function of H * W alone), one chain per thread in
+ *   pixel order, rows and slabs combined in a fixed order, no atomics: the same operands give the same bits in every run.
+ *   workspace: hrv_instnorm_jvp_workspace_elems doubles.
+ * hrv_instnorm_jvp_bwd_nhwc_f32: the element-wise pass; reads the record, writes tbar and cbar (fp64 arithmetic, one rounding to
+ *   fp32 per output).  cin (nullable): an adjoint of x that arrives by another path (the ordinary InstanceNorm backward of the
+ *   primal feature's adjoint), added in fp64 before that rounding.  P = 1 gives y = 0, tbar = 0 and cbar = cin, all finite.
+ * C is the padded channel count (C % 4 == 0; mean / rstd are [N][C]); every tensor is a channel slice [coff, coff + C) of an NHWC
+ * tensor with pixel stride cstride (both multiples of 4, base pointers 16-byte aligned).  tbar / cbar must not alias an input. */
+typedef struct {
+  const float* x;     /* the InstanceNorm input c */
+  const float* mean;  const float* rstd;
+  const float* f;     /* lrelu(y): its sign is the mask */
+  const float* t;     /* tangent of x */
+  const float* df;    /* adjoint of fdot */
+  const float* cin;   /* nullable */
+  float* tbar;  float* cbar;
+  double* record;     /* [N][C][5] */
+  double* workspace;  /* the stats launch only; the element-wise launch ignores it (may be NULL) */
+  int32_t N, H, W, C;
+  int32_t x_cstride, x_coff, f_cstride, f_coff, t_cstride, t_coff, df_cstride, df_coff, cin_cstride, cin_coff;
+  int32_t tbar_cstride, tbar_coff, cbar_cstride, cbar_coff;
+  float slope;
+  int32_t reserved;
+} hrv_instnorm_jvp_t;
+int64_t hrv_instnorm_jvp_workspace_elems(int32_t N, int32_t H, int32_t W, int32_t C);
+int hrv_instnorm_jvp_stats_nhwc_f32(const hrv_instnorm_jvp_t* d, hrv_stream_t stream);
+int hrv_instnorm_jvp_bwd_nhwc_f32(const hrv_instnorm_jvp_t* d, hrv_stream_t stream);
+/* The seed of the tangent pass.  d_in [N][H][W][Cp] (dense, Cp % 4 == 0): the gradient of sum_n S_n w.r.t. the assembled input
+ * [parse (Ca) ; image (Cb) ; pad].  v (same shape) = d_in * (1.0f / N) on the image channels [Ca, Ca + Cb) and exactly 0 on every
+ * other channel, whatever d_in holds there (a select, not a product).  part: double [N][hrv_r1_seed_slots()], the per-slot sums of
+ * squares of the image channels (fp64; pixel i of a sample belongs to slot (i / 256) % slots; fixed order, no atomics).  The same
+ * call then runs one finalize block: sums[n] = sum of the slots (fixed tree), out[0] = penalty = (sum_n sums[n]) / N and
+ * out[1] = gamma / 2 * penalty, both rounded once to fp32.  Nothing is read back. */
+int hrv_r1_seed_slots(void);
+int hrv_r1_seed_nhwc_f32(const float* d_in, int32_t N, int32_t H, int32_t W, int32_t Cp, int32_t Ca, int32_t Cb, float gamma,
+                         float* v, double* part, double* sums, float* out, hrv_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

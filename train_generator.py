@@ -43,6 +43,10 @@ on the MI355X-native hot path.
     zero counts; two launches and one small copy) is appended to ``<tensorboard_dir>/<name>/layer_stats.jsonl``; the printed line
     names the top parameters by gradient norm, ``--board`` records ``Layers/{G,D}/*``.  ``--layer_stats_on_skip`` (with
     ``--skip_nonfinite``) reports right after a skipped step; it reads the guard record after every step, a host synchronisation.
+  * ``--r1_gamma G`` (default 0 = off; ``--r1_interval 16``): the R1 gradient penalty G / 2 * E_real ||dD/dx||^2 as a separate lazy
+    phase behind the discriminator step of every ``--r1_interval``-th iteration, exact, by a tangent pass through the PatchGAN
+    (hr_viton_amd.r1) on fp32 operands, on the un-augmented real images; the phase is eager.  In those iterations the printed line
+    gains ``D_r1`` and ``r1_pen`` and ``--board`` records ``Loss/dis/r1`` and ``Reg/r1_penalty``.
 Bug-fixes of the reference call sites: tocg(input1, input2) arity, load_checkpoint arity,
 Adam betas as floats.
 """
@@ -73,6 +77,7 @@ from hr_viton_amd.optim import (Adam, add_ema_args, add_guard_args, add_layer_st
                                 check_layer_stats_args, guard_scalars, layer_stats_from_opt)
 from hr_viton_amd.parallel import broadcast_module  # noqa: E402
 from hr_viton_amd.pipeline import generator_train_step, make_generator_inputs  # noqa: E402
+from hr_viton_amd.r1 import add_r1_args, r1_from_opt, r1_line  # noqa: E402
 from hr_viton_amd.validate import (generator_validation_lpips, load_validation_lpips, val_items_loader,  # noqa: E402
                                    validation_due)
 from hr_viton_amd.vgg import VGGLoss  # noqa: E402
@@ -158,6 +163,7 @@ def get_opt(argv=None):
     add_diffaug_args(p)
     add_ada_args(p)
     add_lecam_args(p)
+    add_r1_args(p)
     opt = p.parse_args(argv)
     opt.gpu_ids = [int(s) for s in str(opt.gpu_ids).split(",") if s.strip() and int(s) >= 0]
     return opt
@@ -198,6 +204,7 @@ class _Validation(object):
         self.ema_eval = False               # --ema_eval: the test passes run on opt_g's averaged weights (main sets it)
         self.lecam = None                   # --lecam / --d_stats: the D step's loss head (main sets it)
         self.aug = None                     # --ada_target / --ada_fixed_p: the adaptive augmentation (main sets it)
+        self.r1 = None                      # --r1_gamma: the lazy R1 phase (main sets it)
 
     def weights(self):
         """The context the test passes run in: the generator's averaged weights with --ema_eval, the raw ones otherwise."""
@@ -236,6 +243,9 @@ class _Validation(object):
                 self.board.add_scalar(tag, val, s)
         for tag, val in ada_scalars(self.aug):                       # (nothing without --ada_target / --ada_fixed_p)
             self.board.add_scalar(tag, val, s)
+        if "D_R1" in losses:                                        # (nothing without --r1_gamma, or between two phases)
+            self.board.add_scalar("Loss/dis/r1", float(losses["D_R1"].mean()), s)
+            self.board.add_scalar("Reg/r1_penalty", float(self.r1.last["r1_penalty"]), s)
         if opt.num_test_visualize > 0:
             vb = self.vis_batch()
             with self.weights():
@@ -341,6 +351,7 @@ def main(argv=None):
     if ada is not None and ada.adaptive and not float(getattr(opt, "lecam", 0.0) or 0.0):
         opt.d_stats = True           # the controller follows the head's r_t: the head with weight 0
     lecam = lecam_from_opt(opt)      # (None without --lecam / --d_stats: the four GANLoss calls, nothing allocated)
+    r1 = r1_from_opt(opt)            # (None without --r1_gamma: nothing allocated or launched)
     lam = lambda step: 1.0 - max(0, step * 1000 + opt.load_step - opt.keep_step) / float(opt.decay_step + 1)  # noqa: E731
     sched_g = torch.optim.lr_scheduler.LambdaLR(opt_g, lr_lambda=lam)
     sched_d = torch.optim.lr_scheduler.LambdaLR(opt_d, lr_lambda=lam)
@@ -362,6 +373,7 @@ def main(argv=None):
         validation.ema_eval = bool(ema) and bool(getattr(opt, "ema_eval", False))
         validation.lecam = lecam
         validation.aug = ada
+        validation.r1 = r1
     # (None without --layer_stats_count / --layer_stats_on_skip: nothing allocated or launched; rank 0 reports -- the gradient
     # buffers are the all-reduced ones, every rank would report the same)
     layers = layer_stats_from_opt(opt, [("G", opt_g, generator), ("D", opt_d, discriminator)])
@@ -376,9 +388,11 @@ def main(argv=None):
         record = opt.board and validation is not None and validation_due(step, opt.tensorboard_count)       # :364
         aux = {} if record else None
         x, parse7 = make_generator_inputs(opt, tocg, batch, aux=aux)
+        kw = {} if lecam is None else {"lecam": lecam}
+        if r1 is not None and r1.due(step):      # the lazy R1 phase behind the D step, every --r1_interval iterations
+            kw["r1"] = r1
         losses, _ = generator_train_step(opt, generator, discriminator, crit_gan, crit_feat, crit_vgg, opt_g, opt_d, x,
-                                         parse7, batch["image"], sync_g, sync_d, aux=aux, aug=aug,
-                                         **({} if lecam is None else {"lecam": lecam}))
+                                         parse7, batch["image"], sync_g, sync_d, aux=aux, aug=aug, **kw)
         layer_text = layers.after_step(step + 1, validation.board if opt.board else None) if layers is not None else ""
         if record:
             validation.record(tocg, generator, step, losses, batch, aux, aux["output"])
@@ -391,7 +405,7 @@ def main(argv=None):
             lg = sum(v.item() for k, v in losses.items() if not k.startswith("D_"))
             print("step: %8d, time: %.3f, G_loss: %.4f, G_adv_loss: %.4f, D_loss: %.4f, D_fake_loss: %.4f, D_real_loss: %.4f"
                   % (step + 1, t, lg, losses["GAN"].item(), ld, losses["D_Fake"].item(), losses["D_Real"].item())
-                  + guard_line(opt_g, opt_d) + lecam_line(lecam, losses) + ada_line(ada) + layer_text, flush=True)
+                  + guard_line(opt_g, opt_d) + lecam_line(lecam, losses) + ada_line(ada) + r1_line(r1, losses) + layer_text, flush=True)
         if (step + 1) % opt.save_count == 0 and rank == 0:
             save_checkpoint(generator, os.path.join(opt.checkpoint_dir, opt.name, "gen_step_%06d.pth" % (step + 1)), opt)
             save_checkpoint(discriminator, os.path.join(opt.checkpoint_dir, opt.name, "dis_step_%06d.pth" % (step + 1)), opt)
